@@ -6,13 +6,18 @@ text embedding pre-cached and every input already resident in HBM (configs[1] of
 process per GPU, each rank samples its own 128-motion shard of a 128*N batch (weak scaling) and the final samples
 are all-gathered with RCCL inside the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 works from a bare shell for every N: with N > 1 and no torchrun environment the script re-launches itself as
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>`
 (one rank per GPU over RCCL); launched by torchrun directly (RANK / WORLD_SIZE set) it just joins the group.
 
-Prints ONE JSON line on rank 0.  Besides the contract fields it carries
+Prints ONE JSON line on rank 0: the headline (`value` in motions/s, `ms_per_step` = one timed p_sample_loop), the
+configuration, the process group (`ranks`) and the identity of the build.  A plain run does nothing else: it sets up,
+warms up, times the K steps and prints.  `--dump-outputs DIR` writes the samples of the last timed step as
+DIR/samples.npy (float32; inputs are seeded, so the same arguments give the same inputs in every run).
+
+`--full` adds every other measurement, each a run of its own after the headline:
   roofline      the dominant kernel class (encoder GEMMs) against the MFMA peak it runs on, from hipEvent pairs the
                 library records around every launch of one extra, untimed-for-throughput loop (mdm_profile_*),
   kernel_ms     per-kernel-class totals of that loop,
@@ -22,8 +27,9 @@ Prints ONE JSON line on rank 0.  Besides the contract fields it carries
   small_batch   the same loop at batch 1 / 6 / 10 (what sample/generate.py runs by default; B1 = configs[0]'s shape), ms per call,
   trans_dec     the same loop on the reference's trans_dec + DistilBERT text-to-motion denoiser (README.md:254) at the headline batch,
   cpu_baseline  BASELINE.json configs[0]: the whole 50-step CFG loop at batch 1 on this box's host cores, twice -- the
-                reference's own p_sample_loop where the upstream tree is mounted, else the oracle port (N = 1, rank 0),
-  ranks         what the process group looked like (backend, world size) -- the evidence that RCCL carried the gather.
+                reference's own p_sample_loop where the upstream tree is mounted, else the oracle port (N = 1, rank 0).
+`ranks`, in every line, shows what the process group looked like (backend, world size) -- the evidence that RCCL carried
+the gather.
 """
 import argparse
 import hashlib
@@ -59,10 +65,15 @@ def parse_args(argv=None):
     ap.add_argument("--diffusion-steps", type=int, default=50)
     ap.add_argument("--precision", default="f16x3", choices=["f16x3", "f32"],
                     help="arithmetic of the encoder GEMMs (include/mdm_hip.h mdm_set_precision)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: roofline / kernel_ms (one profiled pass), f32_mode, "
+                         "steps1000, small_batch, trans_dec, dip and cpu_baseline (the --no-* options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the samples the last timed step returned (rank 0: the gathered batch) as DIR/samples.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the f32_mode, steps1000 and dip sub-records")
     ap.add_argument("--no-steps1000", action="store_true", help="skip the 1000-step (BASELINE.json configs[2]) sub-record")
-    ap.add_argument("--quick", action="store_true", help="the headline line only: no sub-records, no CPU baseline")
+    ap.add_argument("--quick", action="store_true", help="with --full: roofline / kernel_ms only, no sub-records, no CPU baseline")
     ap.add_argument("--no-small-batch", action="store_true", help="skip the B = 1 / 6 / 10 latency sub-record")
     # test infrastructure (tests/test_round2_cpu.py::test_bench_self_launches_two_ranks_from_a_bare_shell): the same launcher / sharding / gather / JSON code on CPU --
     # gloo ranks, kernels in the CPU emulator, a tiny model.  Never a measurement.
@@ -349,6 +360,26 @@ def pmc_traffic_per_gemm_launch():
         return None, False, f"{PMC_PROFILE} unreadable ({type(e).__name__})"
 
 
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """--dump-outputs: each array as DIR/<name>.npy in float32.  An array too large for the budget is replaced by a fixed,
+    seeded sample of its rows along dim 0, sorted; DIR/<name>_rows.npy (float64) then holds the indices of those rows."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    budget = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // len(arrays)
+    for name, t in arrays.items():
+        x = t.detach().float().cpu().numpy()
+        if x.nbytes > budget:
+            row_bytes = x.nbytes // x.shape[0]
+            keep = budget // (row_bytes + 8)
+            rows = np.sort(np.random.default_rng(seed).choice(x.shape[0], keep, replace=False))
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+            x = x[rows]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(x))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     a = parse_args(argv)
@@ -408,6 +439,7 @@ def main(argv=None):
         sync()
 
     rank_ms = {}     # label -> per-rank [loop milliseconds] of the last timed() call (a straggler shows as max >> min)
+    last_out = {}    # label -> the gathered samples of the last timed pass
 
     def timed(passes, warmup, seed0, label="headline"):
         for w in range(warmup):
@@ -441,11 +473,15 @@ def main(argv=None):
         rank_ms[label] = per_rank
         assert out.shape[0] == GB and bool(torch.isfinite(out).all())
         rank_ms["gathered_shape"] = list(out.shape)
+        last_out[label] = out
         return dt
 
     dt = timed(a.steps, a.warmup, 100)
     rank_ms["headline"] = list(rank_ms["headline"])
     headline_shape = list(rank_ms["gathered_shape"])
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"samples": last_out["headline"]})
+    last_out.clear()
 
     def flush_c_stdio():
         # RCCL printf()s a version banner into C stdio's buffer at communicator creation; flushed only at exit it would land
@@ -456,15 +492,17 @@ def main(argv=None):
         except Exception:
             pass
 
-    # ---- per-kernel-class timing of one more pass (rank 0's GPU), hipEvents on the launch stream
     eng = mdm.engine()
-    eng.profile(True)
-    one_pass(999)
-    sync()
-    prof = eng.profile_read()
-    eng.profile(False)
+    prof = None
+    if a.full:
+        # ---- per-kernel-class timing of one more pass (rank 0's GPU), hipEvents on the launch stream
+        eng.profile(True)
+        one_pass(999)
+        sync()
+        prof = eng.profile_read()
+        eng.profile(False)
 
-    extras = world == 1 and not a.no_extras and not a.emulate
+    extras = a.full and world == 1 and not a.no_extras and not a.emulate
     f32_mode = dip = None
     if extras and a.precision != "f32":
         # the same workload on the exact-fp32 MFMA kernels (the on-device parity reference): one warm-up + one timed pass
@@ -485,7 +523,7 @@ def main(argv=None):
     trans_dec = None
     if extras and a.precision != "f32" and not a.no_small_batch and a.layers == 8 and a.latent_dim == 512:
         trans_dec = measure_trans_dec(dev, sync, T, DS)
-    if extras or (world > 1 and not a.no_extras):
+    if extras or (a.full and world > 1 and not a.no_extras):
         # BASELINE.json configs[4] (DiP, 256 motions over 8 GPUs = 32 per GPU) at EVERY world size since round 5: each rank
         # generates its 32 motions (Philox streams by global sample index), the final all_gather is inside the timed region.
         # N > 1: this leg has only ever run as one rank on real hardware (no multi-GPU box has been offered); a
@@ -500,11 +538,7 @@ def main(argv=None):
             dip = bench_dip.measure(dev, rank=rank, world=world, B=32, steps=3, warmup=1, cpu=False, small_batch=(world == 1))
 
     if rank == 0:
-        traffic, traffic_stale, traffic_src = pmc_traffic_per_gemm_launch()
         motions_s = GB * a.steps / dt
-        lin = prof["linear"]
-        ach = lin["flops"] / (lin["ms"] * 1e-3) / 1e12 if lin["ms"] > 0 else 0.0
-        peak = PEAKS_TFLOPS[a.precision]
         x3 = a.precision == "f16x3"
         fwd = algorithmic_flops_per_forward(T)
         line = {
@@ -532,22 +566,27 @@ def main(argv=None):
             "finite_check_in_timed_region": False,   # asserted on the last sample behind the clock (rounds 1-3: inside, ~0.1 ms per loop)
             "sample_steps_per_s": round(motions_s * DS, 1),
             "model_tflops": round(motions_s * DS * 2 * fwd / 1e12, 2),
-            "roofline": {"bound": "mfma",
-                         "kernel": ("gemm_x3_kernel" if x3 else "gemm_f32_kernel<RowMajor,RowMajor,Linear>")
-                         + " (encoder GEMMs: in_proj, out_proj, linear1, linear2)",
-                         "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(ach / peak, 4),
-                         "traffic": traffic, "traffic_stale": traffic_stale, "traffic_unit": "bytes/launch",
-                         "traffic_source": traffic_src,
-                         "algorithmic_bytes": ALGORITHMIC_GEMM_BYTES_PER_LAUNCH if x3 else None,
-                         "launches": lin["launches"],
-                         "avg_launch_us": round(lin["ms"] * 1e3 / max(lin["launches"], 1), 2),
-                         "executed_mfma_tflops": round(ach * (3 if x3 else 1), 2),
-                         "peak_basis": ("dense fp16 MFMA (v_mfma_f32_32x32x16_f16) 2.5 PFLOP/s; `achieved` counts the "
-                                        "ALGORITHMIC fp32 flops 2MNK, the kernel executes 3x that on the matrix pipe, so "
-                                        "frac <= 1/3 by construction" if x3 else
-                                        "exact-fp32 MFMA (v_mfma_f32_32x32x2_f32), MI355X_MICROARCH.md")},
-            "kernel_ms": {k: round(v["ms"], 3) for k, v in prof.items()},
         }
+        if prof is not None:
+            traffic, traffic_stale, traffic_src = pmc_traffic_per_gemm_launch()
+            lin = prof["linear"]
+            ach = lin["flops"] / (lin["ms"] * 1e-3) / 1e12 if lin["ms"] > 0 else 0.0
+            peak = PEAKS_TFLOPS[a.precision]
+            line["roofline"] = {"bound": "mfma",
+                                "kernel": ("gemm_x3_kernel" if x3 else "gemm_f32_kernel<RowMajor,RowMajor,Linear>")
+                                + " (encoder GEMMs: in_proj, out_proj, linear1, linear2)",
+                                "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(ach / peak, 4),
+                                "traffic": traffic, "traffic_stale": traffic_stale, "traffic_unit": "bytes/launch",
+                                "traffic_source": traffic_src,
+                                "algorithmic_bytes": ALGORITHMIC_GEMM_BYTES_PER_LAUNCH if x3 else None,
+                                "launches": lin["launches"],
+                                "avg_launch_us": round(lin["ms"] * 1e3 / max(lin["launches"], 1), 2),
+                                "executed_mfma_tflops": round(ach * (3 if x3 else 1), 2),
+                                "peak_basis": ("dense fp16 MFMA (v_mfma_f32_32x32x16_f16) 2.5 PFLOP/s; `achieved` counts the "
+                                               "ALGORITHMIC fp32 flops 2MNK, the kernel executes 3x that on the matrix pipe, so "
+                                               "frac <= 1/3 by construction" if x3 else
+                                               "exact-fp32 MFMA (v_mfma_f32_32x32x2_f32) peak of the MI355X")}
+            line["kernel_ms"] = {k: round(v["ms"], 3) for k, v in prof.items()}
         if f32_mode is not None:
             line["f32_mode"] = f32_mode
         if steps1000 is not None:
@@ -558,7 +597,7 @@ def main(argv=None):
             line["trans_dec"] = trans_dec
         if dip is not None:
             line["dip"] = dip
-        if world == 1 and not a.no_cpu_baseline and not a.emulate:
+        if a.full and world == 1 and not a.no_cpu_baseline and not a.emulate:
             line["cpu_baseline"] = cpu_baseline(state, T, DS)
     if dist.is_initialized():
         dist.barrier()

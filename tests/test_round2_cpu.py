@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from helpers import ROOT, maxabs, orc
+from oracle import ref_harness
 from oracle.synth import synth_state_dict, synth_state_dict_hostile, synth_y, synth_y_hostile
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -94,7 +95,7 @@ def test_bench_self_launches_two_ranks_from_a_bare_shell():
     from emu_lib import emu
     emu()                                              # build the emulator once, before the ranks race for it
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--emulate", "--layers", "1", "--latent-dim", "256",
-           "--batch", "2", "--frames", "6", "--diffusion-steps", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+           "--batch", "2", "--frames", "6", "--diffusion-steps", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=_clean_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -112,6 +113,55 @@ def test_bench_self_launches_two_ranks_from_a_bare_shell():
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
 
 
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """A plain `bench.py` run times the K steps and prints the headline line, nothing else (no profiled pass, no sub-records:
+    those are `--full`'s); `--dump-outputs DIR` writes the samples the last timed step returned as DIR/samples.npy (float32),
+    and two runs with the same arguments dump the same samples (seeded inputs).  One rank, kernels in the emulator, tiny model."""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
+    from emu_lib import emu
+    emu()
+    B, T = 2, 6
+    dumps = []
+    for run in range(2):
+        d_out = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--emulate", "--layers", "1", "--latent-dim", "256",
+               "--batch", str(B), "--frames", str(T), "--diffusion-steps", "2", "--steps", "2", "--warmup", "1",
+               "--dump-outputs", str(d_out)]
+        r = subprocess.run(cmd, env=_clean_env(), capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["n_gpus"] == 1
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+        assert {"metric", "unit", "dtype"} <= set(d)
+        for k in ("roofline", "kernel_ms", "f32_mode", "steps1000", "small_batch", "trans_dec", "dip", "cpu_baseline"):
+            assert k not in d, k
+        assert sorted(os.listdir(d_out)) == ["samples.npy"]
+        x = np.load(d_out / "samples.npy")
+        assert x.dtype == np.float32 and x.shape == (B, 263, 1, T) and np.isfinite(x).all()
+        dumps.append(x)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_bench_dump_outputs_samples_rows_of_an_output_above_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs keeps all files within 64 MB: a larger output is replaced by a fixed, seeded sample of its rows, whose indices
+    go to <name>_rows.npy."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 << 10)
+    x = torch.arange(64 * 263, dtype=torch.float32).reshape(64, 263)
+    files = []
+    for run in range(2):
+        bench.dump_outputs(str(tmp_path / f"run{run}"), {"samples": x})
+        files.append({f: np.load(tmp_path / f"run{run}" / f) for f in sorted(os.listdir(tmp_path / f"run{run}"))})
+        assert sum(os.path.getsize(tmp_path / f"run{run}" / f) for f in files[-1]) <= 64 << 10
+    assert sorted(files[0]) == ["samples.npy", "samples_rows.npy"]
+    rows = files[0]["samples_rows.npy"]
+    assert rows.dtype == np.float64 and 0 < len(rows) < 64 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(files[0]["samples.npy"], x.numpy()[rows.astype(np.int64)])
+    assert all(np.array_equal(files[0][f], files[1][f]) for f in files[0])
+
+
 def test_bench_dry_run_at_the_real_world_size_of_eight_ranks():
     """VERDICT r05 item 7 / SURVEY 8e: BASELINE.json configs[3] / [4] run on 8 GPUs and no multi-GPU box has been offered to this
     repository -- so the launcher is exercised at the REAL world size on CPU: `python bench.py --gpus 8 --emulate` from a bare shell
@@ -123,7 +173,7 @@ def test_bench_dry_run_at_the_real_world_size_of_eight_ranks():
     from emu_lib import emu
     emu()
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--emulate", "--layers", "1", "--latent-dim", "256",
-           "--batch", "1", "--frames", "6", "--diffusion-steps", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+           "--batch", "1", "--frames", "6", "--diffusion-steps", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--full"]
     env = _clean_env()
     env["OMP_NUM_THREADS"] = "1"
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
@@ -142,7 +192,8 @@ def test_bench_dry_run_at_the_real_world_size_of_eight_ranks():
     assert "NOT a measurement" in dip["data"]
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/utils/model_util.py"), reason="needs the reference tree (build container)")
+@pytest.mark.skipif(not os.path.isfile(os.path.join(ref_harness.REFERENCE_ROOT, "utils", "model_util.py")),
+                    reason="needs the upstream reference source tree (MDM_REFERENCE_ROOT), which the repository does not hold")
 def test_integration_md_drop_in_launcher_and_reference_handover():
     """tests/dropin_replay.py: the rebinding of INTEGRATION.md section 1 through the REFERENCE's create_model_and_diffusion /
     load_model_wo_clip / collate, generate.py:93-158's call sequence, and the hand-over of cond_fn / PLMS / foreign models
