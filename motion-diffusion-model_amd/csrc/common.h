@@ -381,6 +381,9 @@ __device__ __forceinline__ void static_for(F&& f) {
 __device__ __forceinline__ void lds_read16(p16x8& dst, const unsigned char* base, uint32_t byte_off) {
   emu::lds_issue(&dst, base + byte_off, 16);   // EARLY mode: immediate; LATE mode: withheld until a covering lds_wait
 }
+__device__ __forceinline__ void lds_refill16(p16x8& slot, const unsigned char* base, uint32_t byte_off) {
+  emu::lds_issue(&slot, base + byte_off, 16);
+}
 template <int N> __device__ __forceinline__ void lds_wait(p16x8&, p16x8&) { emu::lgkm_wait(N); }
 template <int N> __device__ __forceinline__ void lds_wait(p16x8&, p16x8&, p16x8&, p16x8&) { emu::lgkm_wait(N); }
 template <int N> __device__ __forceinline__ void lds_wait(p16x8&, p16x8&, p16x8&, p16x8&, p16x8&, p16x8&) { emu::lgkm_wait(N); }
@@ -390,6 +393,12 @@ __device__ __forceinline__ void lds_wait(p16x8&, p16x8&, p16x8&, p16x8&, p16x8&,
 // `lds_addr` = 32-bit LDS byte address (lds_addr_of), IMM = compile-time byte offset < 65536
 template <int IMM> __device__ __forceinline__ void lds_read16(p16x8& dst, uint32_t lds_addr) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(lds_addr), "i"(IMM));
+}
+// IN-PLACE flavour (cf. gload16_refill): the slot's old value stays live in these very registers up to this read, so a ring of
+// such slots is pinned to its registers and no MFMA result is ever allocated where a fragment read lands next (an MFMA write
+// followed by an LDS write of the same VGPR is a wait-state hazard hipcc does not pad for inline asm: tools/hazard_audit.py rule B)
+template <int IMM> __device__ __forceinline__ void lds_refill16(p16x8& slot, uint32_t lds_addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(slot) : "v"(lds_addr), "i"(IMM));
 }
 template <int N> __device__ __forceinline__ void lds_wait(p16x8& a, p16x8& b) {
   asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "i"(N));

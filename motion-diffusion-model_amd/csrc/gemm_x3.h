@@ -1,6 +1,6 @@
 // Split-precision ("f16x3"; round 1: "bf16x3") MFMA GEMM for the encoder's dense contractions:
 //     C[m][n] = sum_k A[m][k] * W[n][k],   A = Ah + Al,  W = Wh + Wl  (16-bit planes: fp16 by default, common.h kSplitF16 / split_p16)
-//             ~ sum_k  Ah*Wh + Ah*Wl + Al*Wh            three v_mfma_f32_32x32x16_f16 passes, fp32 accumulate.
+//             ~ sum_k  Ah*Wh + Ah*Wl + Al*Wh            three fp16 MFMA passes, fp32 accumulate.
 //
 // Why: the reference computes these `addmm`s in fp32 (model/mdm.py:77-84 -> torch TransformerEncoderLayer) and
 // BASELINE's parity bar is 1e-3 max-abs over a 50-step guided trajectory.  gfx950 has no TF32; exact-fp32 MFMA
@@ -17,8 +17,15 @@
 // global_load_dwordx4 -- weights never pass through LDS (a wave's 32 output columns are private to it, so staging them
 // in LDS bought nothing and cost an LDS-DMA write plus an LDS read per byte).
 //
+// Instruction shape (round 7).  The product's pipelined loop (PIPE, 208-row tiles) runs the whole tile on v_mfma_f32_16x16x32_f16:
+// per wave 13 row slices of 16 x 2 column halves of f32x4 accumulators (104 VGPRs), the A fragment of a slice one ds_read_b128 per
+// plane, the W fragments read from the same fragment-ordered planes through a per-lane remap (M16 in the kernel below).  Under the
+// power limit that shape delivers more FLOP/s than 32x32x16 at equal cycles per FLOP: in_proj 251 -> 232 us per launch, headline
+// +8.4 % same box (profiles/r07a_m16.md).  The step-synchronous loop (InputProcess) stays on 32x32x16, with its last 16-row slice on
+// 16x16x32; the round-6 pipelined form (32x32x16) remains in the probe library (MDM_X3_M32=1).
+//
 // Machine mapping (gfx950).  WAVES waves per PERSISTENT workgroup, each wave owning 32 output columns x all 7 row
-// sub-tiles of the tile (7 accumulators = 112 VGPRs):
+// sub-tiles of the tile (7 accumulators = 112 VGPRs; 104 on 208-row tiles):
 //     WAVES = 8 (default)  224 x 256 tiles, one workgroup per CU (66-97 KB of LDS, <= 256 VGPRs)
 //     WAVES = 4            224 x 128 tiles, two independent workgroups per CU, which hide each other's barriers, LDS-DMA
 //                          latency and epilogues -- and re-read the activation panels twice as often from L2.
@@ -82,6 +89,17 @@ constexpr int X3P_WAIT_WS = 0, X3P_WAIT_MID = 0;
 constexpr int X3P_WAIT_WS = 6, X3P_WAIT_MID = 3;
 #else
 constexpr int X3P_WAIT_WS = 12, X3P_WAIT_MID = 7;
+#endif
+// ... and of the 16x16x32 form (M16), whose queue holds per step and wave  A(g+3) x nA | W(g+2) x 4  (nA >= 3):
+//   step start, slots W(g):  younger = A(g+2) + W(g+1) = 3 + 4                      (STRICT: W(g+1) = 4)
+//   middle, own A(g+1):      younger = W(g) + A(g+2) + W(g+1) = 4 + 3 + 4            (STRICT: A(g+2) = 3)
+// (ORDERED, the start-of-step wait already retires A(g+1), which is older than W(g); the middle wait states the need)
+#if defined(MDM_X3_PIPE_WDRAIN)
+constexpr int X3M_WAIT_WS = 0, X3M_WAIT_MID = 0;
+#elif defined(MDM_X3_PIPE_STRICT)
+constexpr int X3M_WAIT_WS = 4, X3M_WAIT_MID = 3;
+#else
+constexpr int X3M_WAIT_WS = 7, X3M_WAIT_MID = 11;
 #endif
 constexpr int x3_patch_base(int ring) { return ring * X3_A_STAGE; }   // 57344 (2 stages) / 114688 (4)
 constexpr int X3_PATCH_BYTES = 8 * 32 * 4;                       // per wave: 8 rows x 32 columns fp32
@@ -252,13 +270,18 @@ struct X3Cursor {
 // 208 x 256 tile: four waves x 64 columns, ONE workgroup per CU, up to 512 registers per lane (accumulators 208, W slots 64), every
 // A fragment read from LDS feeds two column blocks -- half the LDS fragment traffic and half the rendezvous partners of the
 // 8-wave form.  Pipelined loop only.
+// M16 (round 7, the product form): the pipelined 8-wave loop with the WHOLE 208-row tile on v_mfma_f32_16x16x32_f16 -- 13 row
+// slices x 2 column halves of f32x4 accumulators per wave (see the k-loop below); the 32x32x16 form (M16 = false) is compiled into
+// the probe library only.
 template <int WAVES, int ACT, int RES, bool OUT_F32, bool OUT_PLANES, bool OUT_QKV, int ABL, bool FOLD = false,
-          bool OSTAT = false, bool EMBED = false, bool T16 = false, bool F6 = false, bool PIPE = false, int NCB = 1>
+          bool OSTAT = false, bool EMBED = false, bool T16 = false, bool F6 = false, bool PIPE = false, int NCB = 1,
+          bool M16 = false>
 __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X3Operand A, X3Weights W, X3Epilogue ep, int M, int N,
                                                                      int K, int rows_per_tile, int tiles_n, int total) {
   MDM_DYN_SMEM(unsigned char, lds);
   static_assert(!PIPE || (T16 && (WAVES == 8 || (WAVES == 4 && NCB == 2)) && !F6), "the pipelined k-loop exists for 208-row (T16), 256-column tiles");
   static_assert(NCB == 1 || (NCB == 2 && PIPE && WAVES == 4), "two column blocks per wave: the pipelined 4-wave form only");
+  static_assert(!M16 || (PIPE && WAVES == 8 && NCB == 1 && ABL == 0), "the 16x16x32 form: pipelined, 8 waves, no ablations");
   constexpr int RINGN = PIPE ? X3_PIPE_RING : X3_A_RING;   // A stages in LDS
   constexpr int NBLK = WAVES * NCB;                        // 32-column blocks of a tile (the LDS layout is per block)
   constexpr int X3_WAVES = WAVES, X3_TN = 32 * NBLK, X3_A_PIECES = x3_a_pieces(WAVES);
@@ -417,7 +440,12 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
     tile_origin(wv, m0w, n0w);
     wtile = (uint32_t)((n0w >> 5) + wid * NCB) * (uint32_t)wk16 * 512u;   // (column block cb: + cb * wk16 * 512)
   };
-  auto aim_w = [&]() { wso = wtile + (uint32_t)wkk * 1024u + (uint32_t)lane * 8u; };
+  // M16: the fragment-ordered planes serve the 16x16x32 B operand of column half c through a per-lane remap -- lane l reads block
+  // k/16 = 2 step + (l >> 5), slot 16 c + (l & 15) + 32 ((l >> 4) & 1): every 16 lanes one contiguous 256 bytes.  load_w_half's
+  // `ks` is then the column half (+128 elements) instead of the k sub-step (+512).
+  const uint32_t lane_wo = M16 ? (uint32_t)((lane >> 5) * 512 + ((lane & 15) + 32 * ((lane >> 4) & 1)) * 8) : (uint32_t)lane * 8u;
+  constexpr uint32_t W_HALF = M16 ? 128u : 512u;
+  auto aim_w = [&]() { wso = wtile + (uint32_t)wkk * 1024u + lane_wo; };
   auto advance_w = [&]() {
     if (++wkk == nk) {
       wkk = 0;
@@ -428,7 +456,7 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
     constexpr int q = decltype(q_tag)::value;
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
-      const uint32_t o = wso + (uint32_t)cb * (uint32_t)wk16 * 512u + 512u * (uint32_t)ks;
+      const uint32_t o = wso + (uint32_t)cb * (uint32_t)wk16 * 512u + W_HALF * (uint32_t)ks;
 #ifdef MDM_X3_PIPE_NOGUARD
       gload16_async(wsh[q * NCB + cb], W.hi + o);
       gload16_async(wsl[q * NCB + cb], W.lo + o);
@@ -488,14 +516,21 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
     tile_origin(v, m0, n0);
     f32x16 accs_[NCB][NT32];     // [column block of the wave][row sub-tile]
     f32x4 acc16s_[NCB][2];       // T16: rows 192-207 x columns 0-15 / 16-31 of each column block
+    constexpr int NS16 = 2 * X3_MSUB - 1;                   // M16: 13 row slices of 16
+    f32x4 accm_[M16 ? NS16 : 1][2];                         // M16: [row slice][column half], 104 VGPRs like the 32x32 form
+    if constexpr (M16) {
 #pragma unroll
-    for (int cb = 0; cb < NCB; ++cb) {
+      for (int s = 0; s < NS16; ++s) accm_[s][0] = accm_[s][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else {
 #pragma unroll
-      for (int t = 0; t < NT32; ++t)
+      for (int cb = 0; cb < NCB; ++cb) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) accs_[cb][t][e] = 0.f;
-      acc16s_[cb][0] = f32x4{0.f, 0.f, 0.f, 0.f};
-      acc16s_[cb][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < NT32; ++t)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) accs_[cb][t][e] = 0.f;
+        acc16s_[cb][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+        acc16s_[cb][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
     }
     f32x16 (&acc)[NT32] = accs_[0];       // the one-block forms (step-synchronous loop) work on block 0
     f32x4 (&acc16)[2] = acc16s_[0];
@@ -556,7 +591,99 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
     unsigned long long dbg_t0 = 0, dbg_w0 = 0, dbg_w1 = 0, dbg_bar = 0;
     if constexpr ((ABL & 128) != 0) dbg_t0 = x3_now();
 #endif
-    if constexpr (PIPE) {
+    if constexpr (M16) {
+      // ================= pipelined k-loop on v_mfma_f32_16x16x32_f16 (round 7) =================
+      // The streams, stages, waits and the rendezvous of the 32x32x16 form below; the matrix work is 13 elements per 32-deep step,
+      // one per 16-row slice s: two ds_read_b128 (Ah, Al of rows 16 s + (lane & 15), k chunk lane >> 4 -- the T16 read pattern,
+      // conflict-free) and six MFMAs, the three products of each column half interleaved (acc[s][0], acc[s][1], ...: the two
+      // chains hide each other's dependency).  Under the power limit the 16x16x32 shape delivers more FLOP/s than 32x32x16 at the
+      // same cycles per FLOP (MI355X_MICROARCH.md, "DVFS give-back").
+      //   * both W column halves of step g are read by every element, so slots W0 / W1 of the step are refilled together for
+      //     g + 2 behind its last MFMA (cover: one step);
+      //   * fragment ring: element e uses slot e % 3, the last element slot 3 -- 13 is not a multiple of 3, and the reads of the
+      //     next step's elements 0 / 1 (slots 0 / 1), issued at elements 11 / 12, must not land on a slot still in use.
+      constexpr int NE = NS16, DEPTH = 2, RING = DEPTH + 1, XB = NE / 2;
+      auto slot = [](int e) constexpr { return e == NE - 1 ? RING : e % RING; };
+      //   * the ring is read IN PLACE (common.h lds_refill16): its registers are never an MFMA destination
+      p16x8 ah[RING + 1] = {}, al[RING + 1] = {};
+#ifndef MDM_EMU
+      const uint32_t lane_a = lds_base + fa16 - 192 * 64;   // slice s: + s * 1024 (the swizzle (row >> 2) & 3 does not depend on s)
+#endif
+      auto issue_reads = [&](auto e_tag, uint32_t stg) __attribute__((always_inline)) {
+        constexpr int e = decltype(e_tag)::value;
+#ifdef MDM_EMU
+        lds_refill16(ah[slot(e)], lds + stg * X3_A_STAGE, fa16 - 192 * 64 + e * 1024);
+        lds_refill16(al[slot(e)], lds + stg * X3_A_STAGE, X3_A_BYTES + fa16 - 192 * 64 + e * 1024);
+#else
+        lds_refill16<e * 1024>(ah[slot(e)], lane_a + stg * X3_A_STAGE);
+        lds_refill16<X3_A_BYTES + e * 1024>(al[slot(e)], lane_a + stg * X3_A_STAGE);
+#endif
+      };
+      auto pipe_step = [&](auto par_tag) __attribute__((always_inline)) {
+        constexpr int PAR = decltype(par_tag)::value, W0 = 2 * PAR, W1 = 2 * PAR + 1;
+        const uint32_t cur = (uint32_t)gs & 3u, nxt = (uint32_t)(gs + 1) & 3u, fill = (uint32_t)(gs + 3) & 3u;
+        // slots W(g) (issued at the end of step g-2) landed
+        vmem_wait<X3M_WAIT_WS>(wsh[W0], wsl[W0], wsh[W1], wsl[W1]);
+        static_for<NE>([&](auto e_tag) __attribute__((always_inline)) {
+          constexpr int e = decltype(e_tag)::value;
+          // ---- 1. reads of the element DEPTH ahead (past the step: elements 0, 1 of step g+1, from the next stage)
+          if constexpr (e + DEPTH < NE) issue_reads(std::integral_constant<int, e + DEPTH>{}, cur);
+          else issue_reads(std::integral_constant<int, e + DEPTH - NE>{}, nxt);
+          // ---- 2. the middle of the step: own pieces of A(g+1) landed, then the rendezvous makes them visible
+          if constexpr (e == XB) {
+            vmem_wait<X3M_WAIT_MID + X3P_MID_SLACK>(wsh[W0], wsl[W0], wsh[W1], wsl[W1]);
+#ifndef MDM_EMU
+            __builtin_amdgcn_sched_barrier(0);
+#endif
+            wg_barrier_nodrain();   // A(g+1) visible to every wave; every wave is past step g-1, whose stage A(g+3) refills
+#ifndef MDM_EMU
+            __builtin_amdgcn_sched_barrier(0);
+#endif
+          }
+          // ---- 3. this element's reads retired (those of the DEPTH younger elements stay in flight)
+          lds_wait<2 * DEPTH>(ah[slot(e)], al[slot(e)]);
+#ifndef MDM_EMU
+          __builtin_amdgcn_sched_barrier(0);  // the MFMAs below must not be hoisted above the wait (rule 18)
+#endif
+          // ---- 4. matrix work: per column half al*wh, ah*wl, ah*wh (the product order of every form)
+#pragma unroll
+          for (int c = 0; c < 2; ++c) accm_[e][c] = mfma16_p16(al[slot(e)], wsh[W0 + c], accm_[e][c]);
+#pragma unroll
+          for (int c = 0; c < 2; ++c) accm_[e][c] = mfma16_p16(ah[slot(e)], wsl[W0 + c], accm_[e][c]);
+#pragma unroll
+          for (int c = 0; c < 2; ++c) accm_[e][c] = mfma16_p16(ah[slot(e)], wsh[W0 + c], accm_[e][c]);
+#ifndef MDM_EMU
+          __builtin_amdgcn_sched_barrier(0);
+#endif
+          // ---- 5. one LDS-DMA piece of A(g+3) rides behind each of the elements that follow the barrier
+          if constexpr (e >= XB && e < XB + X3_A_PIECES) piece_a(ca, e - XB, (int)fill);
+#ifndef MDM_EMU
+          __builtin_amdgcn_sched_barrier(0);
+#endif
+        });
+        // both W slots of the step are free: refill in place for g+2; then both streams move on
+        aim_w();
+        load_w_half(0, std::integral_constant<int, W0>{});
+        load_w_half(1, std::integral_constant<int, W1>{});
+        advance_w();
+        advance_a(ca);
+        ++gs;
+      };
+      // prime the fragment pipeline of this tile: its first stage was made visible by the previous step's barrier / the prologue
+      static_for<DEPTH>([&](auto d_tag) __attribute__((always_inline)) { issue_reads(d_tag, (uint32_t)gs & 3u); });
+      for (int kt = 0; kt < nk; kt += 2) {
+        pipe_step(std::integral_constant<int, 0>{});
+        if (kt == 0 && v + gstride < total) {   // the next tile's per-column vectors (see the 32x32x16 form)
+          int m0n, n0n;
+          tile_origin(v + gstride, m0n, n0n);
+          cvec_dma(n0n, tile_parity ^ 1);
+        }
+        pipe_step(std::integral_constant<int, 1>{});
+      }
+      // the last step's reads of the next tile's elements 0, 1: retired and dropped (re-primed behind the epilogue)
+      lds_wait<0>(ah[0], al[0], ah[1], al[1]);
+      wait_all_slots();
+    } else if constexpr (PIPE) {
       // ================= pipelined k-loop (round 3) =================
       // What the step-synchronous loop below pays per 32-deep step -- a full vmcnt(0) drain of loads issued at most one step
       // earlier, a rendezvous of all eight waves behind it, and a cold restart of the fragment-read pipeline (measured: a
@@ -974,7 +1101,17 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
     // the VALU work of the next (a wave's LDS operations execute in order).
     auto patch_write = [&](auto j_tag) __attribute__((always_inline)) {
       constexpr int j = decltype(j_tag)::value, t = j / 4, g = j % 4;
-      if constexpr (j < 4 * NT32) {
+      if constexpr (M16) {
+        // 16x16 accumulators: round j = rows 8 (j % 2) .. + 7 of slice j / 2, held by the lanes with lane >> 5 == j % 2 (as below)
+        if constexpr (j < NROUNDS) {
+          if (h == j % 2) {
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) patch[((e + 4 * (g16 & 1)) << 5) + 16 * cb + r16] = accm_[j / 2][cb][e];
+          }
+        }
+      } else if constexpr (j < 4 * NT32) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) patch[((e + 4 * h) << 5) + r] = acc[t][4 * g + e];
       } else if constexpr (T16 && j < NROUNDS) {
@@ -1008,6 +1145,34 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
           p16_t* vhp = ep.qkv.vh + ((shq * ep.qkv.NKT) * AX_HD + d0 + r) * 32 + 8 * h;
           p16_t* vlp = ep.qkv.vl + ((shq * ep.qkv.NKT) * AX_HD + d0 + r) * 32 + 8 * h;
           const int nkt = ep.qkv.NKT;
+          if constexpr (M16) {
+            // 16x16 accumulators: keys 16 s + 4 (lane >> 4) + e of slice s = key tile s / 2, 16-key group s % 2, positions
+            // 4 ((g16 >> 1) + 2 (g16 & 1)) + e of the group (the T16 store below, on every slice); keys 208-223 are never written
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+              const int cl = 16 * cb + r16;                      // this lane's column inside the wave's 32
+              const float b16 = cvec[wblk * 32 + cl];
+              const float c16 = FOLD ? cvec[256 + wblk * 32 + cl] : 0.f;
+              const size_t o0 = (shq * ep.qkv.NKT * AX_HD + d0 + cl) * 32 + 4 * ((g16 >> 1) + 2 * (g16 & 1));
+#pragma unroll
+              for (int s = 0; s < NS16; ++s) {
+                if ((s >> 1) < nkt) {
+                  float vv[4];
+#pragma unroll
+                  for (int e = 0; e < 4; ++e) {
+                    if constexpr (FOLD) {
+                      const float2 st = atab[16 * s + 4 * g16 + e];
+                      vv[e] = st.y * (accm_[s][cb][e] * accs - st.x * c16) + b16;
+                    } else {
+                      vv[e] = accm_[s][cb][e] * accs + b16;
+                    }
+                  }
+                  const size_t o = o0 + (size_t)(s >> 1) * (AX_HD * 32) + 16 * (s & 1);
+                  split4_store(ep.qkv.vh + o, ep.qkv.vl + o, make_float4(vv[0], vv[1], vv[2], vv[3]));
+                }
+              }
+            }
+          } else {
 #pragma unroll
           for (int t = 0; t < NT32; ++t) {
             if (t < nkt) {
@@ -1054,6 +1219,7 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
               }
             }
           }
+          }   // !M16
         } else {
           // Q / K rows: one base pointer per plane, 32-bit offsets
           p16_t* dh = (which == 0 ? ep.qkv.qh : ep.qkv.kh) + shq * SPq * AX_HD + d0 + pc4;
@@ -1343,7 +1509,8 @@ inline int x3_waves_setting() { return 8; }   // the 4-wave form is compiled int
 #endif
 
 template <int WAVES, int ACT, int RES, bool OUT_F32, bool OUT_PLANES, bool OUT_QKV, int ABL, bool FOLD = false,
-          bool OSTAT = false, bool EMBED = false, bool T16 = false, bool F6 = false, bool PIPE = false, int NCB = 1>
+          bool OSTAT = false, bool EMBED = false, bool T16 = false, bool F6 = false, bool PIPE = false, int NCB = 1,
+          bool M16 = false>
 inline int launch_gemm_x3_w(const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N, int K,
                                 int rpt, hipStream_t stream) {
   constexpr int NBLK = WAVES * NCB;          // 32-column blocks per tile: the LDS layout is per block
@@ -1353,7 +1520,7 @@ inline int launch_gemm_x3_w(const X3Operand& A, const X3Weights& W, const X3Epil
   const int tiles_m = (M + rpt - 1) / rpt, tiles_n = (N + TN - 1) / TN;
   const int total = tiles_m * tiles_n;
   static_assert(!(F6 && T16), "the f16f6 k-loop has no 16-row sub-tile yet");
-  auto kfn = &gemm_x3_kernel<WAVES, ACT, RES, OUT_F32, OUT_PLANES, OUT_QKV, ABL, FOLD, OSTAT, EMBED, T16, F6, PIPE, NCB>;
+  auto kfn = &gemm_x3_kernel<WAVES, ACT, RES, OUT_F32, OUT_PLANES, OUT_QKV, ABL, FOLD, OSTAT, EMBED, T16, F6, PIPE, NCB, M16>;
   if (T16 && rpt > X3_TM - 16) return -2;
   if (PIPE && (K / X3_BK) % 2 != 0) return -2;   // the pipelined k-loop is unrolled over step pairs
   if (!x3_has_col_scale(ACT, RES) && ep.scale_cols > 0) return -2;   // (this instantiation compiles the column scale out)
@@ -1408,7 +1575,8 @@ inline bool x3_pipe_setting(int kind = 0) {
 //   kind 4  OutputProcess                       FOLD -> fp32
 //   kind 5  InputProcess                        + positional rows, planes to the token rows of every branch (EMBED)
 // WIDE (round 4): the pipelined loop as four waves x 64 columns, one wave per SIMD (kernel header, NCB = 2)
-template <bool T16, bool PIPE = false, bool WIDE = false>
+// M16 (round 7): the pipelined loop on 16x16x32 MFMAs (kernel header) -- the product's pipelined form
+template <bool T16, bool PIPE = false, bool WIDE = false, bool M16 = false>
 inline int launch_gemm_x3_ln_t(int kind, const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N,
                                    int K, int rpt, hipStream_t s) {
 #ifdef MDM_PROBES   // (measured 12-18 % slower per launch, profiles/r04d_wide.md: instantiated in the probe library only)
@@ -1424,12 +1592,13 @@ inline int launch_gemm_x3_ln_t(int kind, const X3Operand& A, const X3Weights& W,
   }
 #endif
   switch (kind) {
-    case 0: return launch_gemm_x3_w<8, ACT_NONE, 0, false, false, true, 0, true, false, false, T16, false, PIPE>(A, W, ep, M, N, K, rpt, s);
-    case 1: return launch_gemm_x3_w<8, ACT_NONE, 2, false, true, false, 0, false, true, false, T16, false, PIPE>(A, W, ep, M, N, K, rpt, s);
-    case 2: return launch_gemm_x3_w<8, ACT_NONE, 3, false, true, false, 0, false, true, false, T16, false, PIPE>(A, W, ep, M, N, K, rpt, s);
-    case 3: return launch_gemm_x3_w<8, ACT_GELU, 0, false, true, false, 0, true, false, false, T16, false, PIPE>(A, W, ep, M, N, K, rpt, s);
-    case 4: return launch_gemm_x3_w<8, ACT_NONE, 0, true, false, false, 0, true, false, false, T16, false, PIPE>(A, W, ep, M, N, K, rpt, s);
-    case 5:   // InputProcess: K = 288 is nine steps -- stays on the step-synchronous loop
+    case 0: return launch_gemm_x3_w<8, ACT_NONE, 0, false, false, true, 0, true, false, false, T16, false, PIPE, 1, M16>(A, W, ep, M, N, K, rpt, s);
+    case 1: return launch_gemm_x3_w<8, ACT_NONE, 2, false, true, false, 0, false, true, false, T16, false, PIPE, 1, M16>(A, W, ep, M, N, K, rpt, s);
+    case 2: return launch_gemm_x3_w<8, ACT_NONE, 3, false, true, false, 0, false, true, false, T16, false, PIPE, 1, M16>(A, W, ep, M, N, K, rpt, s);
+    case 3: return launch_gemm_x3_w<8, ACT_GELU, 0, false, true, false, 0, true, false, false, T16, false, PIPE, 1, M16>(A, W, ep, M, N, K, rpt, s);
+    case 4: return launch_gemm_x3_w<8, ACT_NONE, 0, true, false, false, 0, true, false, false, T16, false, PIPE, 1, M16>(A, W, ep, M, N, K, rpt, s);
+    case 5:   // InputProcess: K = 288 is nine steps -- stays on the step-synchronous loop (32x32x16)
+      if constexpr (M16) return -2;
       return launch_gemm_x3_w<8, ACT_NONE, 1, false, true, false, 0, false, false, true, T16>(A, W, ep, M, N, K, rpt, s);
     default: return -2;
   }
@@ -1446,12 +1615,28 @@ inline bool x3_t16_setting() {
   return true;
 #endif
 }
+// The pipelined loop runs on 16x16x32 MFMAs (M16); probe library: MDM_X3_M32=1 selects the 32x32x16 form for same-box A/B runs
+// (the product library instantiates the 16x16x32 form only)
+inline bool x3_m16_setting() {
+#ifdef MDM_PROBES
+  static const bool on = [] {
+    const char* e = getenv("MDM_X3_M32");
+    return !(e != nullptr && e[0] == '1');
+  }();
+  return on;
+#else
+  return true;
+#endif
+}
 inline int launch_gemm_x3_ln(int kind, const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N,
                                  int K, int rpt, hipStream_t s) {
   if (rpt <= X3_TM - 16 && x3_t16_setting()) {
     if (kind != 5 && (K / X3_BK) % 2 == 0 && x3_pipe_setting(kind)) {
+#ifdef MDM_PROBES
       if (x3_wide_setting()) return launch_gemm_x3_ln_t<true, true, true>(kind, A, W, ep, M, N, K, rpt, s);
-      return launch_gemm_x3_ln_t<true, true>(kind, A, W, ep, M, N, K, rpt, s);
+      if (!x3_m16_setting()) return launch_gemm_x3_ln_t<true, true>(kind, A, W, ep, M, N, K, rpt, s);
+#endif
+      return launch_gemm_x3_ln_t<true, true, false, true>(kind, A, W, ep, M, N, K, rpt, s);
     }
     return launch_gemm_x3_ln_t<true>(kind, A, W, ep, M, N, K, rpt, s);
   }
@@ -1558,9 +1743,12 @@ inline int launch_gemm_x3_qkv(const X3Operand& A, const X3Weights& W, const X3Ep
       if (x3_wide_setting())
         return launch_gemm_x3_w<4, ACT_NONE, 0, false, false, true, 0, false, false, false, true, false, true, 2>(A, W, ep, nseq * S,
                                                                                                                    3 * D, D, S, s);
+      if (!x3_m16_setting())
+        return launch_gemm_x3_w<8, ACT_NONE, 0, false, false, true, 0, false, false, false, true, false, true>(A, W, ep, nseq * S,
+                                                                                                                3 * D, D, S, s);
 #endif
-      return launch_gemm_x3_w<8, ACT_NONE, 0, false, false, true, 0, false, false, false, true, false, true>(A, W, ep, nseq * S,
-                                                                                                              3 * D, D, S, s);
+      return launch_gemm_x3_w<8, ACT_NONE, 0, false, false, true, 0, false, false, false, true, false, true, 1, true>(
+          A, W, ep, nseq * S, 3 * D, D, S, s);
     }
     return launch_gemm_x3_w<8, ACT_NONE, 0, false, false, true, 0, false, false, false, true>(A, W, ep, nseq * S, 3 * D, D,
                                                                                                  S, s);
