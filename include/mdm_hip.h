@@ -355,6 +355,18 @@ int mdm_attention_x3(const float* qkv_dev, float* out_dev, const int32_t* length
 int mdm_recover_from_ric(const float* x_dev, const float* mean_dev, const float* std_dev, float* out_dev, int32_t B,
                          int32_t T, int32_t njoints_feat, int32_t joints, void* stream);
 
+/* Post-sampling transform of the rot6d (action-to-motion) families, on the device: the SMPL joint positions of
+ *   model.rot2xyz(x, mask, pose_rep='rot6d', glob=True, translation=True, jointstype='smpl', vertstrans=True, beta=0)
+ * (model/rotation2xyz.py:17-90, utils/rotation_conversions.py rotation_6d_to_matrix, smplx lbs batch_rigid_transform).
+ * x_dev [B, njoints_in = J + 1, 6, T] (the sampler's output: J joint rotations in 6D, then the translation row, of which the
+ * first 3 features are read); mask_dev [B, T] uint8 (nullptr: every frame valid; a masked frame's rotations are not read and
+ * its joints are 0 before the translation is added); rest_joints [J * 3] HOST array, the rest-pose joints
+ * J_regressor . v_template; parents [J] HOST array, parents[0] = -1 and 0 <= parents[i] < i (SMPL's kintree_table[0]);
+ * out_dev [B, J, 3, T]: posed joint minus posed root plus (translation_t - translation_0).  J <= 24, T <= 4096.
+ * The tables travel as kernel arguments: no device allocation, capture-safe. */
+int mdm_rot6d_to_smpl_joints(const float* x_dev, const uint8_t* mask_dev, const float* rest_joints, const int32_t* parents,
+                             float* out_dev, int32_t B, int32_t T, int32_t njoints_in, int32_t J, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = [
     "mdm_set_precision", "mdm_linear_x3", "mdm_linear_x3_scratch_bytes", "mdm_attention_x3", "mdm_attention_x3_scratch_bytes",
     "mdm_recover_from_ric", "mdm_workspace_bytes_dec", "mdm_forward_dec", "mdm_workspace_bytes_dec_loop",
     "mdm_sample_loop_dec", "mdm_weights_in_range", "mdm_set_option", "mdm_get_option", "mdm_set_time_add",
+    "mdm_rot6d_to_smpl_joints",
 ]
 # include/mdm_hip_probe.h: exported by the probe build only
 PROBE_SYMBOLS = ["mdm_debug_set", "mdm_debug_get", "mdm_linear_f16f6", "mdm_linear_f16f6_scratch_bytes", "mdm_probe_in_proj"]
@@ -113,6 +114,7 @@ class MdmLib:
             "mdm_set_option": (C.c_int, [vp, i32, i32]),
             "mdm_get_option": (C.c_int, [vp, i32, P(i32)]),
             "mdm_set_time_add": (C.c_int, [vp, vp, i32]),
+            "mdm_rot6d_to_smpl_joints": (C.c_int, [vp, vp, P(f32), P(i32), vp, i32, i32, i32, i32, vp]),
         }
         probe_sig = {
             "mdm_debug_set": (C.c_int, [C.c_int, C.c_int]),

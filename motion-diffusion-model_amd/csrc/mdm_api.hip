@@ -31,6 +31,7 @@
 #include "../../lab/csrc_probe/gemm_f16f6.h"
 #endif
 #include "motion_recover.h"
+#include "smpl_joints.h"
 
 using namespace mdm;
 
@@ -794,6 +795,27 @@ int mdm_recover_from_ric(const float* x, const float* mean, const float* stdv, f
   auto k = &recover_from_ric_kernel;
   MDM_LAUNCH(k, dim3(B), dim3(256), (size_t)3 * T * sizeof(float), static_cast<hipStream_t>(stream), x, mean, stdv, out, T,
              njoints_feat, joints);
+  return rt_launch_status();
+}
+
+int mdm_rot6d_to_smpl_joints(const float* x, const uint8_t* mask, const float* rest_joints, const int32_t* parents, float* out,
+                             int32_t B, int32_t T, int32_t njoints_in, int32_t J, void* stream) {
+  if (!x || !rest_joints || !parents || !out) return fail(MDM_EINVAL, "mdm_rot6d_to_smpl_joints: null pointer");
+  if (B <= 0 || T <= 0 || J < 1) return fail(MDM_EINVAL, "mdm_rot6d_to_smpl_joints: need B >= 1, T >= 1 and J >= 1");
+  if (njoints_in != J + 1)
+    return fail(MDM_EINVAL, "mdm_rot6d_to_smpl_joints: njoints_in must be J + 1 (the joint rotations, then the translation row)");
+  if (J > kSmplMaxJoints) return fail(MDM_EUNSUPPORTED, "mdm_rot6d_to_smpl_joints: at most 24 joints");
+  if (T > 4096 || (int64_t)B * T > (1 << 24)) return fail(MDM_EUNSUPPORTED, "mdm_rot6d_to_smpl_joints: at most 4096 frames and 2^24 frames in all");
+  if (parents[0] != -1) return fail(MDM_EINVAL, "mdm_rot6d_to_smpl_joints: parents[0] must be -1 (the root)");
+  for (int i = 1; i < J; ++i)
+    if (parents[i] < 0 || parents[i] >= i)
+      return fail(MDM_EINVAL, "mdm_rot6d_to_smpl_joints: parents[" + std::to_string(i) + "] must lie in [0, " + std::to_string(i) + ")");
+  SmplFkTables tab;
+  if (smpl_fk_tables(rest_joints, parents, J, tab) < 0) return fail(MDM_EUNSUPPORTED, "mdm_rot6d_to_smpl_joints: tree needs too many live transforms");
+  ChainGuard chain_guard(stream);
+  auto k = &smpl_joints_kernel;
+  MDM_LAUNCH(k, dim3((unsigned)(((int64_t)B * T + kSmplLanes - 1) / kSmplLanes)), dim3(kSmplLanes), 0, static_cast<hipStream_t>(stream),
+             x, mask, out, B, T, J, tab);
   return rt_launch_status();
 }
 

@@ -22,6 +22,7 @@ import torch.nn as nn
 from . import _native as nat
 from . import _engine
 from ._engine import Engine
+from .rotation2xyz import Rotation2xyz
 
 
 class PositionalEncoding(nn.Module):
@@ -177,19 +178,6 @@ class EmbedTargetLocMulti(_TargetLocBase):
         return self.target_all_loc_emb(rows)
 
 
-class _IdentityRot2xyz:
-    """Stand-in for model/rotation2xyz.py: for data_rep='hml_vec' the callers use pose_rep='xyz', for which the
-    reference returns its input unchanged (rotation2xyz.py:20-21; sample/generate.py:167)."""
-
-    def __init__(self):
-        self.smpl_model = nn.Module()
-
-    def __call__(self, x, mask=None, pose_rep="xyz", **kw):
-        if pose_rep != "xyz":
-            raise NotImplementedError("SMPL forward kinematics is outside the MI355X hot path (SURVEY.md 2)")
-        return x
-
-
 class MDM(nn.Module):
     def __init__(self, modeltype, njoints, nfeats, num_actions, translation, pose_rep, glob, glob_rot,
                  latent_dim=256, ff_size=1024, num_layers=8, num_heads=4, dropout=0.1,
@@ -282,7 +270,8 @@ class MDM(nn.Module):
             # the text encoder itself (CLIP / DistilBERT) is outside the hot path: callers cache y['text_embed']
             self.clip_model = self._try_load_clip(clip_version) if self.text_encoder_type == 'clip' else None
         self.output_process = OutputProcess(data_rep, self.input_feats, latent_dim, njoints, nfeats)
-        self.rot2xyz = _IdentityRot2xyz()
+        # model/mdm.py:135; a plain attribute (no state-dict keys), the SMPL file is read at the first non-xyz call
+        self.rot2xyz = Rotation2xyz(device="cpu", dataset=self.dataset, _native_lib=self._native_lib)
         self._engine = None
         self._engine_key = None
 

@@ -39,7 +39,7 @@ def get_cond_mode(args):
 def get_model_args(args, data=None):
     """utils/model_util.py:24-71.  The hml_vec datasets (263 / 251 features) or, for the action datasets (humanact12 / uestc), the
     SMPL defaults of :33-37: 25 joints x 6 rot6d features, `num_actions` from the dataset object (:29-32; args.num_actions when no
-    dataset object is at hand).  SMPL forward kinematics for rendering those (rot2xyz) stays outside the hot path."""
+    dataset object is at hand).  Their SMPL joint positions (model.rot2xyz, jointstype='smpl') come from mdm_amd/rotation2xyz.py."""
     g = vars(args).get
     if args.dataset in _POSE_DIMS:
         njoints, nfeats, data_rep, num_actions = _POSE_DIMS[args.dataset], 1, "hml_vec", 1
