@@ -367,6 +367,68 @@ int mdm_recover_from_ric(const float* x_dev, const float* mean_dev, const float*
 int mdm_rot6d_to_smpl_joints(const float* x_dev, const uint8_t* mask_dev, const float* rest_joints, const int32_t* parents,
                              float* out_dev, int32_t B, int32_t T, int32_t njoints_in, int32_t J, void* stream);
 
+/* The full SMPL body pass of model/rotation2xyz.py:17-92 over model/smpl.py:64-97 and smplx's lbs, on the device: shape blend,
+ * pose blend shapes, linear blend skinning of every vertex, joints regressed from the mesh; every pose_rep, jointstype, betas and
+ * glob_rot the reference accepts (additive to ABI 10; kernels: csrc/smpl_mesh.h).
+ *
+ * The model tables are caller-owned fp32 DEVICE arrays, prepared once per model (mdm_amd/smpl_mesh.py does it):
+ *   j0         [J][3]                the rest joints of the mean shape, J_regressor . v_template
+ *   jdirs      [J][3][10]            their shape directions, J_regressor . shapedirs
+ *   blend      [3][KP][Vpad]         B'_c[k][v]: rows 0 .. (J-1)*9 - 1 posedirs, then the 10 shapedirs, then v_template, then zeros;
+ *                                    KP = ((J - 1) * 9 + 10 + 1) rounded up to 4, Vpad = V rounded up to 32, zero beyond V
+ *   weights_t  [24][Vpad]            the skinning weights transposed, zero beyond J and V
+ *   sel_blend, sel_weights_t         the same two tables gathered at the n_sel vertices that follow the J joints in smplx's joint
+ *                                    list (VertexJointSelector), Vpad = n_sel rounded up to 32; may be null when n_sel = 0
+ *   extra_t    [V][n_extra]          J_regressor_extra transposed; may be null when n_extra = 0
+ *   parents    [J] HOST              parents[0] = -1, 0 <= parents[i] < i                                         J <= 24 */
+typedef struct mdm_smpl_model {
+  const float* j0;
+  const float* jdirs;
+  const float* blend;
+  const float* weights_t;
+  const float* sel_blend;
+  const float* sel_weights_t;
+  const float* extra_t;
+  const int32_t* parents;
+  int32_t J, V, n_sel, n_extra;
+} mdm_smpl_model_t;
+
+#define MDM_SMPL_ROT6D 0   /* pose_rep: features per rotation row 6, 3, 9, 4 */
+#define MDM_SMPL_ROTVEC 1
+#define MDM_SMPL_ROTMAT 2
+#define MDM_SMPL_ROTQUAT 3
+
+/* One call's arguments (rotation2xyz.py:17-19).  n_points = 0: jointstype 'vertices', out_dev [B, V, 3, T], no root subtraction.
+ * n_points >= 1 (at most 64): a joints family, out_dev [B, n_points, 3, T]; point_map (HOST) indexes smplx's joint list extended
+ * as model/smpl.py:86-96 does -- 0 .. J-1 the posed joints, J .. J+n_sel-1 the selected vertices, then the n_extra regressed
+ * joints -- and root_point is the POINT whose position is subtracted (JOINTSTYPE_ROOT).  Only what the map names is computed. */
+typedef struct mdm_smpl_call {
+  int32_t pose_rep;            /* MDM_SMPL_*                                                                     */
+  int32_t glob;                /* 0: glob_rot_mat is every frame's global orient, every rotation row is a body joint */
+  int32_t translation;         /* 1: the last row of x holds the translation in its first 3 features              */
+  int32_t vertstrans;          /* 1 (with translation): add translation_t - translation_0                          */
+  int32_t n_points;
+  int32_t root_point;
+  const int32_t* point_map;    /* HOST [n_points]                                                                  */
+  const float* glob_rot_mat;   /* HOST [9], row-major; read when glob = 0                                          */
+  float beta1;                 /* betas_dev = null: betas = (0, beta1, 0, ...) for every frame                      */
+} mdm_smpl_call_t;
+
+/* Bytes of workspace mdm_smpl_forward needs; 0 on a bad argument (mdm_last_error says which).  The bound, in floats:
+ *   B * T * (KP + 12 * 24 + 3 + 3 * (J + n_sel + n_extra))     pose features, relative transforms, offsets, joint list
+ *   + 16 * 32 * 3 * V                                           only when the map names a regressed joint: the mesh of 16 tiles
+ *                                                               of 32 frames at a time (42 MB at V = 6890), whatever B and T are */
+size_t mdm_smpl_workspace_bytes(const mdm_smpl_model_t* model, const mdm_smpl_call_t* call, int32_t B, int32_t T);
+
+/* x_dev [B, rows_x, feats_x, T]: rows_x = (glob ? J : J - 1) + (translation ? 1 : 0) and feats_x = the pose_rep's feature count.
+ * mask_dev [B, T] uint8 or null (every frame valid): a masked frame is 0 before the root subtraction and the translation add.
+ * betas_dev [B, 10, T] or null.  rot_out_dev [B, T, rows of rotations, 3, 3] or null: the rotation matrices of the rows of x
+ * (valid frames only are written).  workspace_dev: 16-byte aligned, at least mdm_smpl_workspace_bytes.  No device allocation, no
+ * synchronisation, every kernel on `stream`: capture-safe.  T <= 4096, B * T <= 2^24. */
+int mdm_smpl_forward(const mdm_smpl_model_t* model, const mdm_smpl_call_t* call, const float* x_dev, const uint8_t* mask_dev,
+                     const float* betas_dev, float* out_dev, float* rot_out_dev, int32_t B, int32_t T, int32_t rows_x,
+                     int32_t feats_x, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

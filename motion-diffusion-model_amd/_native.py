@@ -25,7 +25,7 @@ EXPORTED_SYMBOLS = [
     "mdm_set_precision", "mdm_linear_x3", "mdm_linear_x3_scratch_bytes", "mdm_attention_x3", "mdm_attention_x3_scratch_bytes",
     "mdm_recover_from_ric", "mdm_workspace_bytes_dec", "mdm_forward_dec", "mdm_workspace_bytes_dec_loop",
     "mdm_sample_loop_dec", "mdm_weights_in_range", "mdm_set_option", "mdm_get_option", "mdm_set_time_add",
-    "mdm_rot6d_to_smpl_joints",
+    "mdm_rot6d_to_smpl_joints", "mdm_smpl_workspace_bytes", "mdm_smpl_forward",
 ]
 # include/mdm_hip_probe.h: exported by the probe build only
 PROBE_SYMBOLS = ["mdm_debug_set", "mdm_debug_get", "mdm_linear_f16f6", "mdm_linear_f16f6_scratch_bytes", "mdm_probe_in_proj"]
@@ -39,6 +39,22 @@ ARCH = {"trans_enc": 0, "trans_dec": 1}
 class MdmConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("njoints", "nfeats", "latent_dim", "ff_size", "num_layers", "num_heads",
                                          "clip_dim", "max_len", "mask_frames", "arch", "context_len")]
+
+
+class MdmSmplModel(C.Structure):
+    """include/mdm_hip.h mdm_smpl_model_t: device pointers of the prepared SMPL tables (parents: host)."""
+    _fields_ = [(n, C.c_void_p) for n in ("j0", "jdirs", "blend", "weights_t", "sel_blend", "sel_weights_t", "extra_t")] + \
+               [("parents", C.POINTER(C.c_int32))] + [(n, C.c_int32) for n in ("J", "V", "n_sel", "n_extra")]
+
+
+class MdmSmplCall(C.Structure):
+    """include/mdm_hip.h mdm_smpl_call_t."""
+    _fields_ = [(n, C.c_int32) for n in ("pose_rep", "glob", "translation", "vertstrans", "n_points", "root_point")] + \
+               [("point_map", C.POINTER(C.c_int32)), ("glob_rot_mat", C.POINTER(C.c_float)), ("beta1", C.c_float)]
+
+
+SMPL_POSE_REPS = {"rot6d": 0, "rotvec": 1, "rotmat": 2, "rotquat": 3}      # MDM_SMPL_*: feature counts 6, 3, 9, 4
+SMPL_REP_FEATS = {"rot6d": 6, "rotvec": 3, "rotmat": 9, "rotquat": 4}
 
 
 class MdmStep(C.Structure):
@@ -115,6 +131,8 @@ class MdmLib:
             "mdm_get_option": (C.c_int, [vp, i32, P(i32)]),
             "mdm_set_time_add": (C.c_int, [vp, vp, i32]),
             "mdm_rot6d_to_smpl_joints": (C.c_int, [vp, vp, P(f32), P(i32), vp, i32, i32, i32, i32, vp]),
+            "mdm_smpl_workspace_bytes": (sz, [P(MdmSmplModel), P(MdmSmplCall), i32, i32]),
+            "mdm_smpl_forward": (C.c_int, [P(MdmSmplModel), P(MdmSmplCall), vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
         }
         probe_sig = {
             "mdm_debug_set": (C.c_int, [C.c_int, C.c_int]),
