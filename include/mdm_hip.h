@@ -134,6 +134,13 @@ void mdm_destroy(mdm_model_t* m);
  *                                 embeds to with time_embed(t) (+ the mdm_set_time_add row) + pe[0] in every branch), and count the row
  *                                 in `lengths_dev` as context rows are.  0 (default): context rows are embedded prefix frames (DiP). */
 #define MDM_OPT_DEC_TIME_TOKEN 6
+/*   MDM_OPT_ENC_SHARED_LAYER0     1 (default): under guidance (MDM_BRANCH_BOTH) layer 0's in_proj of the trans_enc stack computes the
+ *                                 Q / K / V rows of a sample's frame tokens ONCE and writes them to both branches' operand planes --
+ *                                 the two sequences of a sample differ only in token 0, the condition token, which rides in a pad
+ *                                 row of the sample's 208-row tile (csrc/gemm_x3.h PAIR).  Same products in the same order: results
+ *                                 are bit-identical.  Taken on the sequence-tile route of the f16x3 mode for sequences of at most
+ *                                 207 tokens; every other forward, and 0 (A/B and tests), runs one tile per sequence. */
+#define MDM_OPT_ENC_SHARED_LAYER0 7
 int mdm_set_option(mdm_model_t* m, int32_t key, int32_t value);
 int mdm_get_option(const mdm_model_t* m, int32_t key, int32_t* value);
 

@@ -73,7 +73,10 @@ class Engine:
           'attn_direct_out'       0 (default); 1 = the encoder attention kernel stores its output planes straight from the
                                   accumulators (measured slower, profiles/r05e_attention_direct.md; A/B only)
           'dec_time_token'        a model-structure switch, set by MDM for `emb_trans_dec` checkpoints: 1 = the one context row of a
-                                  context_len = 1 trans_dec model is the timestep embedding (model/mdm.py:256-257), not a prefix frame"""
+                                  context_len = 1 trans_dec model is the timestep embedding (model/mdm.py:256-257), not a prefix frame
+          'enc_shared_layer0'     1 (default) = a guided trans_enc forward on the sequence-tile route computes layer 0's in_proj once
+                                  per sample and writes the frame rows to both branches' planes (bit-identical results; sequences
+                                  of <= 207 tokens), 0 = one tile per sequence (A/B and tests)"""
         if name not in nat.OPTIONS:
             raise ValueError(f"unknown engine option {name!r}: one of {sorted(nat.OPTIONS)}")
         self.lib.check(self.lib.mdm_set_option(self.handle, nat.OPTIONS[name], int(value)), f"mdm_set_option({name})")

@@ -284,14 +284,18 @@ int launch_linear_x3(Profiler* pf, X3Operand a, X3Weights w, const float* bias, 
 }
 
 // in_proj in split precision: tokens -> Q (pre-scaled) / K / V^T operand planes of attention_x3.h
+// pair_B > 0: the nseq = 2 pair_B sequences are the two guidance branches of pair_B samples, equal but for token 0 -- one tile per
+// sample computes S + 1 rows and writes both sequences' planes (gemm_x3.h PAIR; the caller has checked x3_qkv_pairs)
 int launch_in_proj_x3(Profiler* pf, X3Operand a, X3Weights w, const float* bias, const QkvPlanes& qp, int nseq, int S,
-                      int D, float qscale, hipStream_t s) {
+                      int D, float qscale, hipStream_t s, int pair_B = 0) {
   if (D % X3_BK != 0) return fail(MDM_EINVAL, "f16x3 in_proj: latent_dim must be a multiple of 32");
-  ProfScope ps(pf, MDM_PROF_LINEAR, 2.0 * nseq * S * 3.0 * D * (double)D, s);
+  const double rows = pair_B > 0 ? (double)pair_B * (S + 1) : (double)nseq * S;     // the rows actually computed
+  ProfScope ps(pf, MDM_PROF_LINEAR, 2.0 * rows * 3.0 * D * (double)D, s);
   X3Epilogue ep{nullptr, bias, nullptr, nullptr, nullptr, nullptr, nullptr, 3 * D, D, qscale, qp, S, D,
                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1.f, 1, 1, 1};
-  const int rc = launch_gemm_x3_qkv(a, w, ep, nseq, S, D, s);
-  if (rc == -2) return fail(MDM_EUNSUPPORTED, "f16x3 in_proj: sequences longer than 224 tokens");
+  const int rc = launch_gemm_x3_qkv(a, w, ep, nseq, S, D, s, pair_B);
+  if (rc == -2) return fail(MDM_EUNSUPPORTED, pair_B > 0 ? "f16x3 in_proj: the paired layer-0 launch does not cover this shape"
+                                                         : "f16x3 in_proj: sequences longer than 224 tokens");
   return rt_launch_status();
 }
 

@@ -90,7 +90,10 @@ int encoder(mdm_model* m, const Workspace& ws, int nseq, int B, int S, const int
         if (int rc = launch_x3_ln(pf, MDM_PROF_LINEAR, 6, xb, P.in_proj, m->L(l, "self_attn.in_proj_bias"), a, nullptr, nullptr,
                                   nullptr, &ws.qp, M, 3 * D, D, S, D, D, qscale, s)) return rc;
       } else if (l == 0) {
-        if (int rc = launch_in_proj_x3(pf, xb, P.in_proj, m->L(l, "self_attn.in_proj_bias"), ws.qp, nseq, S, D, qscale, s)) return rc;
+        // both guidance branches in one forward: the sequences of a sample differ in token 0 only (embed_frames_x3 writes the frame
+        // tokens once, to both), so layer 0's in_proj runs one tile per SAMPLE (gemm_x3.h PAIR; MDM_OPT_ENC_SHARED_LAYER0)
+        const int pair_B = (m->enc_shared_l0 && nseq == 2 * B && x3_qkv_pairs(S, D)) ? B : 0;
+        if (int rc = launch_in_proj_x3(pf, xb, P.in_proj, m->L(l, "self_attn.in_proj_bias"), ws.qp, nseq, S, D, qscale, s, pair_B)) return rc;
       } else {
         LnArgs a = LN(); a.astat = ws.stat2; a.colsum = F.c_qkv;
         if (int rc = launch_x3_ln(pf, MDM_PROF_LINEAR, 0, xb, F.in_proj, F.b_qkv, a, nullptr, nullptr, nullptr, &ws.qp, M,

@@ -39,8 +39,10 @@
 //   * A tile: global -> LDS by global_load_lds_dwordx4, BK = 32, two stages of Ah|Al [224][32] = 28 KB; the pieces a
 //     wave issues per step ride BETWEEN the MFMA units; the stream has its own (tile, k) cursor one step ahead and
 //     rolls over into the workgroup's next tile, so the pipeline never drains at a tile boundary;
-//   * LDS image: row-major, 64-byte rows, 16-byte chunk index XOR-swizzled with (row>>2)&3 (conflict-free ds_read_b128
-//     groups); LDS-DMA writes lane-linearly, so the swizzle is applied to the per-lane SOURCE address and to the reads
+//   * LDS image: row-major, 64-byte rows, 16-byte chunk index XOR-swizzled with x3_swz((row>>2)&3), x3_swz = (0, 2, 3, 1) (below):
+//     one image whose ds_read_b128 lane groups are conflict-free on the 16x16x32 read pattern AND on both 32x32x16 ones (rounds
+//     1-7 XORed with (row>>2)&3 itself: conflict-free on 32x32x16 only, 2-way on the 16x16x32 reads round 7 moved the tile to);
+//     LDS-DMA writes lane-linearly, so the swizzle is applied to the per-lane SOURCE address and to the reads
 //     (cdna_hip_programming.md rule 21).  Fragment reads are issued through untracked inline-asm ds_reads retired by
 //     counted lgkmcnt waits (common.h lds_read16): hipcc only ever emits lgkmcnt(0) beside an LDS-DMA;
 //   * W fragments for step g+1 are fetched into registers during step g (plain loads, waited with the step's vmcnt);
@@ -54,6 +56,18 @@
 namespace mdm {
 
 constexpr int X3_TM = 224, X3_BK = 32;
+// The A-stage swizzle: the 16-byte chunk c of row `row` is stored at chunk c ^ x3_swz((row >> 2) & 3) of its 64-byte LDS row.  ONE
+// helper for the LDS-DMA source address and for every fragment read, so that the two cannot drift apart.  A ds_read_b128 is
+// served in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} (+32 for the upper half; MI355X_MICROARCH.md, LDS): 16 lanes
+// x 16 bytes over 64 banks x 4 bytes, conflict-free when the 16 (row & 3, stored chunk) pairs differ.
+//   16x16x32 reads  lane -> (row lane & 15, chunk lane >> 4): a group holds row quads q = 0, 3 with chunk c and q = 1, 2 with c ^ 1;
+//                   stored chunks f(0), f(3), f(1) ^ 1, f(2) ^ 1 (^ c) must differ -- the identity gives 0, 3, 0, 3: 2-way
+//                   (measured: SQ_LDS_BANK_CONFLICT 1.79 M -> 22.4 M per in_proj launch, profiles/r07a_m16.md);
+//   32x32x16 reads  lane -> (row lane & 31, chunk 2 ksub + (lane >> 5)): a group holds q = 0, 3, 5, 6 or 1, 2, 4, 7 (mod 4: all
+//                   four) with ONE chunk; any permutation f works.
+// f = (0, 2, 3, 1) is one of the eight permutations that are 1-way on all three patterns (tests/test_host_lds_swizzle.py).
+__host__ __device__ constexpr int x3_swz(int q) { return (((q ^ (q >> 1)) & 1) << 1) | (q >> 1); }
+static_assert(x3_swz(0) == 0 && x3_swz(1) == 2 && x3_swz(2) == 3 && x3_swz(3) == 1, "A-stage swizzle permutation");
 // WAVES waves per workgroup, each owning 32 output columns: 4 -> 224x128 tiles, two workgroups per CU;
 //                                                            8 -> 224x256 tiles, one workgroup per CU (half the
 //                                                                 activation re-reads from L2, waves in lock-step)
@@ -169,6 +183,7 @@ struct X3Epilogue {
   int emb_T, emb_B, emb_nbranch;
   float acc_scale = kX3AccScale;   // accumulators -> value: undoes the 2^8 the weight planes carry (common.h kX3WeightScale)
   int stat_cols = 256;             // columns each partial of astat / rstat covers: 256 (this kernel's OSTAT), 128 (gemm_x3s.h)
+  int pair_B = 0;                  // PAIR (OUT_QKV): samples per guidance branch -- tile b also serves sequence pair_B + b (kernel header)
 };
 
 constexpr bool x3_has_col_scale(int act, int res) { return act == 0 && (res == 0 || res == 1); }
@@ -273,15 +288,22 @@ struct X3Cursor {
 // M16 (round 7, the product form): the pipelined 8-wave loop with the WHOLE 208-row tile on v_mfma_f32_16x16x32_f16 -- 13 row
 // slices x 2 column halves of f32x4 accumulators per wave (see the k-loop below); the 32x32x16 form (M16 = false) is compiled into
 // the probe library only.
+// PAIR (round 8, layer 0's in_proj under guidance): sequences b and pair_B + b of the 2 pair_B the planes hold differ only in token 0
+// (the condition token; the frame tokens are written once to both by the embedding GEMM), so ONE tile serves both: tile rows
+// 0 .. S-1 are sequence b, tile row S -- a pad row of the 208-row tile, S <= 207 -- is loaded from token 0 of sequence pair_B + b.
+// The epilogue writes row 0 to sequence b, rows 1 .. S-1 to both and row S to token 0 of sequence pair_B + b: every Q / K / V^T
+// element keeps its products and their order, a row's position in the tile does not enter them.  M, the grid and the k-loop (its
+// stages, piece dealing and counted waits) are those of a pair_B-sequence launch; only one lane's source offset per plane differs.
 template <int WAVES, int ACT, int RES, bool OUT_F32, bool OUT_PLANES, bool OUT_QKV, int ABL, bool FOLD = false,
           bool OSTAT = false, bool EMBED = false, bool T16 = false, bool F6 = false, bool PIPE = false, int NCB = 1,
-          bool M16 = false>
+          bool M16 = false, bool PAIR = false>
 __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X3Operand A, X3Weights W, X3Epilogue ep, int M, int N,
                                                                      int K, int rows_per_tile, int tiles_n, int total) {
   MDM_DYN_SMEM(unsigned char, lds);
   static_assert(!PIPE || (T16 && (WAVES == 8 || (WAVES == 4 && NCB == 2)) && !F6), "the pipelined k-loop exists for 208-row (T16), 256-column tiles");
   static_assert(NCB == 1 || (NCB == 2 && PIPE && WAVES == 4), "two column blocks per wave: the pipelined 4-wave form only");
   static_assert(!M16 || (PIPE && WAVES == 8 && NCB == 1 && ABL == 0), "the 16x16x32 form: pipelined, 8 waves, no ablations");
+  static_assert(!PAIR || (M16 && OUT_QKV && !FOLD), "the paired tile: layer 0's in_proj (no folded LayerNorm) on the 16x16x32 form");
   constexpr int RINGN = PIPE ? X3_PIPE_RING : X3_A_RING;   // A stages in LDS
   constexpr int NBLK = WAVES * NCB;                        // 32-column blocks of a tile (the LDS layout is per block)
   constexpr int X3_WAVES = WAVES, X3_TN = 32 * NBLK, X3_A_PIECES = x3_a_pieces(WAVES);
@@ -309,8 +331,8 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
 
   // ---- LDS-DMA sources.  A stage image = 28 groups of 1 KB (16 rows x 64 B): groups 0-13 Ah, 14-27 Al.  Wave w issues
   // groups w, w+4, ..., w+24.  Lane -> (row = lane>>2, stored chunk = lane&3); the logical k-chunk it fetches is
-  // stored ^ ((row>>2)&3) = (lane&3) ^ ((lane>>4)&3).  Rows past the tile / matrix are clamped (never stored).
-  const int schunk = (lane & 3) ^ ((lane >> 4) & 3);
+  // stored ^ x3_swz((row>>2)&3) = (lane&3) ^ x3_swz((lane>>4)&3).  Rows past the tile / matrix are clamped (never stored).
+  const int schunk = (lane & 3) ^ x3_swz((lane >> 4) & 3);
   auto aim_a = [&](Cursor& c) {
     int m0, n0;
     tile_origin(c.v, m0, n0);
@@ -321,7 +343,10 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
       const int jj = min(wid + X3_WAVES * i, 25);
       const int q = PIPE ? (jj < 13 ? jj : jj + 1) : min(wid + X3_WAVES * i, X3_A_GROUPS - 1);
       const int ga = (q < 14) ? q : q - 14;
-      const int arow = min(m0 + ga * 16 + (lane >> 2), M - 1);
+      int arow = min(m0 + ga * 16 + (lane >> 2), M - 1);
+      if constexpr (PAIR) {   // tile row S: token 0 of the other branch's sequence (rows_per_tile == S, M == pair_B * S)
+        if (ga * 16 + (lane >> 2) == rows_per_tile) arow = m0 + M;
+      }
       if constexpr ((ABL & 16) != 0) {
         // timing experiment: a k-BLOCKED plane layout ([row/16][k/32][16 rows][32 k]) would make every piece one
         // contiguous KB; the data fetched here is wrong, only the address pattern is representative
@@ -364,12 +389,12 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
     fl[1] = *reinterpret_cast<const p16x8*>(W.lo + o + 512);
   };
 
-  // ---- fragment read offsets (bytes inside a plane tile): row*64 + ((ksub*2 + h) ^ sw)*16, sw = (row>>2)&3
-  const int sw = (r >> 2) & 3;
+  // ---- fragment read offsets (bytes inside a plane tile): row*64 + ((ksub*2 + h) ^ sw)*16, sw = x3_swz((row>>2)&3)
+  const int sw = x3_swz((r >> 2) & 3);
   const int fa = r * 64;                 // + t*2048 per row sub-tile
   // 16-row sub-tile (T16): lane -> (row 192 + (lane&15), k chunk lane>>4)
   const int r16 = lane & 15, g16 = lane >> 4;
-  const int fa16 = (192 + r16) * 64 + ((g16 ^ ((r16 >> 2) & 3)) * 16);
+  const int fa16 = (192 + r16) * 64 + ((g16 ^ x3_swz((r16 >> 2) & 3)) * 16);
 #ifndef MDM_EMU
   const uint32_t lds_base = lds_addr_of(lds);
 #endif
@@ -595,7 +620,7 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
       // ================= pipelined k-loop on v_mfma_f32_16x16x32_f16 (round 7) =================
       // The streams, stages, waits and the rendezvous of the 32x32x16 form below; the matrix work is 13 elements per 32-deep step,
       // one per 16-row slice s: two ds_read_b128 (Ah, Al of rows 16 s + (lane & 15), k chunk lane >> 4 -- the T16 read pattern,
-      // conflict-free) and six MFMAs, the three products of each column half interleaved (acc[s][0], acc[s][1], ...: the two
+      // conflict-free under x3_swz; 2-way under the plain (row >> 2) & 3 of rounds 1-7) and six MFMAs, the three products of each column half interleaved (acc[s][0], acc[s][1], ...: the two
       // chains hide each other's dependency).  Under the power limit the 16x16x32 shape delivers more FLOP/s than 32x32x16 at the
       // same cycles per FLOP (MI355X_MICROARCH.md, "DVFS give-back").
       //   * both W column halves of step g are read by every element, so slots W0 / W1 of the step are refilled together for
@@ -607,7 +632,7 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
       //   * the ring is read IN PLACE (common.h lds_refill16): its registers are never an MFMA destination
       p16x8 ah[RING + 1] = {}, al[RING + 1] = {};
 #ifndef MDM_EMU
-      const uint32_t lane_a = lds_base + fa16 - 192 * 64;   // slice s: + s * 1024 (the swizzle (row >> 2) & 3 does not depend on s)
+      const uint32_t lane_a = lds_base + fa16 - 192 * 64;   // slice s: + s * 1024 (the swizzle x3_swz((row >> 2) & 3) does not depend on s)
 #endif
       auto issue_reads = [&](auto e_tag, uint32_t stg) __attribute__((always_inline)) {
         constexpr int e = decltype(e_tag)::value;
@@ -1154,6 +1179,25 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
               const float b16 = cvec[wblk * 32 + cl];
               const float c16 = FOLD ? cvec[256 + wblk * 32 + cl] : 0.f;
               const size_t o0 = (shq * ep.qkv.NKT * AX_HD + d0 + cl) * 32 + 4 * ((g16 >> 1) + 2 * (g16 & 1));
+              auto vfin = [&](float a) __attribute__((always_inline)) { return a * accs + b16; };   // (!FOLD: one expression for both uses)
+              // PAIR: key 0 of sequence pair_B + b is tile row S -- register S & 3 of slice S >> 4 in the lane of this column whose
+              // lane >> 4 is (S >> 2) & 3.  Every lane finishes that register of its own (the slice and the register are wave-uniform:
+              // no dynamic register index), then the lanes that hold keys 0-3 fetch it across the wave and store it WITH their
+              // keys 1-3, in one 8-byte store per plane: no byte of the other sequence is written twice.
+              float u0 = 0.f;
+              size_t po = 0;
+              if constexpr (PAIR) {
+                const int sS = ep.S >> 4, eS = ep.S & 3;
+#pragma unroll
+                for (int s = 0; s < NS16; ++s) {
+                  if (s == sS) {
+                    const f32x4 a = accm_[s][cb];
+                    u0 = vfin(eS == 0 ? a[0] : eS == 1 ? a[1] : eS == 2 ? a[2] : a[3]);
+                  }
+                }
+                u0 = lane_bcast(u0, r16 + 16 * ((ep.S >> 2) & 3));
+                po = (size_t)ep.pair_B * Hq * ep.qkv.NKT * (AX_HD * 32);
+              }
 #pragma unroll
               for (int s = 0; s < NS16; ++s) {
                 if ((s >> 1) < nkt) {
@@ -1164,11 +1208,15 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
                       const float2 st = atab[16 * s + 4 * g16 + e];
                       vv[e] = st.y * (accm_[s][cb][e] * accs - st.x * c16) + b16;
                     } else {
-                      vv[e] = accm_[s][cb][e] * accs + b16;
+                      vv[e] = vfin(accm_[s][cb][e]);
                     }
                   }
                   const size_t o = o0 + (size_t)(s >> 1) * (AX_HD * 32) + 16 * (s & 1);
                   split4_store(ep.qkv.vh + o, ep.qkv.vl + o, make_float4(vv[0], vv[1], vv[2], vv[3]));
+                  if constexpr (PAIR) {   // the same keys of sequence pair_B + b (pad keys, tile row S among them, stay finite)
+                    const float k0 = (s == 0 && g16 == 0) ? u0 : vv[0];
+                    split4_store(ep.qkv.vh + po + o, ep.qkv.vl + po + o, make_float4(k0, vv[1], vv[2], vv[3]));
+                  }
                 }
               }
             }
@@ -1224,7 +1272,10 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
           // Q / K rows: one base pointer per plane, 32-bit offsets
           p16_t* dh = (which == 0 ? ep.qkv.qh : ep.qkv.kh) + shq * SPq * AX_HD + d0 + pc4;
           p16_t* dl = (which == 0 ? ep.qkv.ql : ep.qkv.kl) + shq * SPq * AX_HD + d0 + pc4;
-          const int nkt = ep.qkv.NKT;
+          // sub-tiles that hold rows to store; PAIR: rows 0 .. S (S a multiple of 32: tile row S opens one more than the planes' NKT)
+          const int nkt = PAIR ? (ep.S + 32) / 32 : ep.qkv.NKT;
+          // PAIR: the same rows of sequence pair_B + b (rows 1 .. S-1 as they are, tile row S as its token 0)
+          const size_t pq = PAIR ? (size_t)ep.pair_B * Hq * SPq * AX_HD : 0;
           patch_write(std::integral_constant<int, 0>{});
           float2 st_cur = row_stats(std::integral_constant<int, 0>{});
           float4 v_cur = zero4();
@@ -1261,7 +1312,16 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
               v4 = finish4(v4, st);
               // tokens past the sequence (only the last sub-tile can hold any when the tile is one sequence of more than
               // 192 tokens) are not stored: the attention kernel never reads Q / K pad rows
-              if (t < X3_MSUB - 1 || tok < ep.S) split4_store(dh + tok * AX_HD, dl + tok * AX_HD, v4);
+              if constexpr (PAIR) {
+                // (tile row S is another sequence's token here: no pad row of sequence b is stored in any sub-tile)
+                if (tok < ep.S) split4_store(dh + tok * AX_HD, dl + tok * AX_HD, v4);
+                if ((unsigned)(tok - 1) < (unsigned)ep.S) {
+                  const int tok2 = tok == ep.S ? 0 : tok;
+                  split4_store(dh + pq + tok2 * AX_HD, dl + pq + tok2 * AX_HD, v4);
+                }
+              } else {
+                if (t < X3_MSUB - 1 || tok < ep.S) split4_store(dh + tok * AX_HD, dl + tok * AX_HD, v4);
+              }
             }
           });
         }
@@ -1510,7 +1570,7 @@ inline int x3_waves_setting() { return 8; }   // the 4-wave form is compiled int
 
 template <int WAVES, int ACT, int RES, bool OUT_F32, bool OUT_PLANES, bool OUT_QKV, int ABL, bool FOLD = false,
           bool OSTAT = false, bool EMBED = false, bool T16 = false, bool F6 = false, bool PIPE = false, int NCB = 1,
-          bool M16 = false>
+          bool M16 = false, bool PAIR = false>
 inline int launch_gemm_x3_w(const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N, int K,
                                 int rpt, hipStream_t stream) {
   constexpr int NBLK = WAVES * NCB;          // 32-column blocks per tile: the LDS layout is per block
@@ -1520,8 +1580,9 @@ inline int launch_gemm_x3_w(const X3Operand& A, const X3Weights& W, const X3Epil
   const int tiles_m = (M + rpt - 1) / rpt, tiles_n = (N + TN - 1) / TN;
   const int total = tiles_m * tiles_n;
   static_assert(!(F6 && T16), "the f16f6 k-loop has no 16-row sub-tile yet");
-  auto kfn = &gemm_x3_kernel<WAVES, ACT, RES, OUT_F32, OUT_PLANES, OUT_QKV, ABL, FOLD, OSTAT, EMBED, T16, F6, PIPE, NCB, M16>;
+  auto kfn = &gemm_x3_kernel<WAVES, ACT, RES, OUT_F32, OUT_PLANES, OUT_QKV, ABL, FOLD, OSTAT, EMBED, T16, F6, PIPE, NCB, M16, PAIR>;
   if (T16 && rpt > X3_TM - 16) return -2;
+  if (PAIR && (rpt + 1 > X3_TM - 16 || ep.pair_B < 1 || M != ep.pair_B * rpt)) return -2;   // tile row S must exist; one tile per sample
   if (PIPE && (K / X3_BK) % 2 != 0) return -2;   // the pipelined k-loop is unrolled over step pairs
   if (!x3_has_col_scale(ACT, RES) && ep.scale_cols > 0) return -2;   // (this instantiation compiles the column scale out)
 #ifndef MDM_EMU
@@ -1733,10 +1794,25 @@ inline int launch_gemm_f16f6(const X3Operand& A, const X3Weights& W, const X3Epi
 }
 #endif
 
-// in_proj: tokens [nseq*S][D] x W [3D][D] -> the attention operand planes; one sequence per tile (tile row == token)
+// Does a guided in_proj launch (2 B sequences of S tokens) take the paired tile (kernel header, PAIR)?  Only the product's
+// pipelined 16x16x32 form has it; everything else runs one tile per sequence.
+inline bool x3_qkv_pairs(int S, int D) {
+  return x3_waves_setting() == 8 && S + 1 <= X3_TM - 16 && x3_t16_setting() && (D / X3_BK) % 2 == 0 && x3_pipe_setting(5) &&
+         !x3_wide_setting() && x3_m16_setting();
+}
+
+// in_proj: tokens [nseq*S][D] x W [3D][D] -> the attention operand planes; one sequence per tile (tile row == token).
+// pair_B > 0 (nseq == 2 pair_B, x3_qkv_pairs): one tile per SAMPLE, written to both of its sequences.
 inline int launch_gemm_x3_qkv(const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int nseq, int S, int D,
-                                  hipStream_t s) {
+                                  hipStream_t s, int pair_B = 0) {
   if (S > X3_TM) return -2;
+  if (pair_B > 0) {
+    if (nseq != 2 * pair_B || !x3_qkv_pairs(S, D)) return -2;
+    X3Epilogue ep2 = ep;
+    ep2.pair_B = pair_B;
+    return launch_gemm_x3_w<8, ACT_NONE, 0, false, false, true, 0, false, false, false, true, false, true, 1, true, true>(
+        A, W, ep2, pair_B * S, 3 * D, D, S, s);
+  }
   if (x3_waves_setting() == 8 && S <= X3_TM - 16 && x3_t16_setting()) {
     if ((D / X3_BK) % 2 == 0 && x3_pipe_setting(5)) {
 #ifdef MDM_PROBES

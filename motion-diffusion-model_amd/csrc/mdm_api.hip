@@ -172,6 +172,10 @@ int mdm_set_option(mdm_model_t* m, int32_t key, int32_t value) {
         return fail(MDM_EINVAL, "mdm_set_option: MDM_OPT_DEC_TIME_TOKEN needs a trans_dec model created with context_len = 1 (the class-token row)");
       m->dec_time_token = value != 0;
       return MDM_OK;
+    case MDM_OPT_ENC_SHARED_LAYER0:
+      if (value != 0 && value != 1) return fail(MDM_EINVAL, "mdm_set_option: MDM_OPT_ENC_SHARED_LAYER0 must be 0 or 1");
+      m->enc_shared_l0 = value != 0;
+      return MDM_OK;
     default:
       return fail(MDM_EINVAL, "mdm_set_option: unknown key " + std::to_string(key));
   }
@@ -195,6 +199,7 @@ int mdm_get_option(const mdm_model_t* m, int32_t key, int32_t* value) {
     case MDM_OPT_DEC_FUSED_SELFATTN: *value = m->fused_selfattn ? 1 : 0; return MDM_OK;
     case MDM_OPT_ATTN_DIRECT_OUT: *value = m->attn_direct ? 1 : 0; return MDM_OK;
     case MDM_OPT_DEC_TIME_TOKEN: *value = m->dec_time_token ? 1 : 0; return MDM_OK;
+    case MDM_OPT_ENC_SHARED_LAYER0: *value = m->enc_shared_l0 ? 1 : 0; return MDM_OK;
     default: return fail(MDM_EINVAL, "mdm_get_option: unknown key " + std::to_string(key));
   }
 }

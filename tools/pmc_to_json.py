@@ -21,7 +21,7 @@ def classify(name):
     <WAVES, ACT, RES, OUT_F32, OUT_PLANES, OUT_QKV, ABL, FOLD, OSTAT, EMBED, T16, F6> read from the END (names arrive
     truncated on the left)."""
     name = name.strip().strip("`")
-    if "gemm_x3_kernel" in name or re.search(r"(true|false)(, (true|false)){4}>", name):
+    if "gemm_x3_kernel" in name or "_x3_kernel<" in name or re.search(r"(true|false)(, (true|false)){4}>", name):
         args = [a.strip() for a in name[name.rfind("<") + 1:name.rfind(">")].split(",")] if "<" in name else \
             [a.strip() for a in name[:name.rfind(">")].split(",")]
         if len(args) >= 11:
@@ -33,6 +33,10 @@ def classify(name):
             # round 4 appended a 14th argument (NCB, an integer): the last argument is then a number, PIPE the one before it
             if args[-1].strip().isdigit() and len(args) >= 13 and args[-2].strip() in ("true", "false"):
                 tail = args[::-1][2:13]
+            # round 7 appended M16 and round 8 PAIR (booleans) behind NCB: the integer is then the second / third argument from the right
+            for behind in (1, 2):
+                if len(args) >= 13 + behind and args[-1 - behind].strip().isdigit() and args[-2 - behind].strip() in ("true", "false"):
+                    tail = args[::-1][2 + behind:13 + behind]
             f6, t16, embed, ostat, fold, abl, qkv, planes, f32, res, act = tail
             b = lambda v: v == "true"   # noqa: E731
             if b(embed):

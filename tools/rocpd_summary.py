@@ -19,7 +19,7 @@ def main(path, by_grid=False):
         n = row[0]
         g = f"{row[1]} | " if (by_grid and grid) else ""
         cnt, tot, avg, mn, mx = row[-5:]
-        print(f"| `{n[:110]}` | {g}{cnt} | {tot / 1e6:.3f} | {avg / 1e3:.2f} | {mn / 1e3:.2f} | {mx / 1e3:.2f} | {100 * tot / total:.2f} |")
+        print(f"| `{n[:118]}` | {g}{cnt} | {tot / 1e6:.3f} | {avg / 1e3:.2f} | {mn / 1e3:.2f} | {mx / 1e3:.2f} | {100 * tot / total:.2f} |")
 
 
 if __name__ == "__main__":
