@@ -436,6 +436,66 @@ int mdm_smpl_forward(const mdm_smpl_model_t* model, const mdm_smpl_call_t* call,
                      const float* betas_dev, float* out_dev, float* rot_out_dev, int32_t B, int32_t T, int32_t rows_x,
                      int32_t feats_x, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The HumanML3D / KIT evaluator (eval/eval_humanml.py): the networks behind EvaluatorMDMWrapper.get_co_embeddings and
+ * get_motion_embeddings (data_loaders/humanml/networks/evaluator_wrapper.py:121-187; modules.py:79-98 MovementConvEncoder,
+ * :311-350 TextEncoderBiGRUCo, :353-386 MotionEncoderBiGRUCo), in exact fp32 (additive to ABI 10; kernels: csrc/evaluator.h).
+ * Every weight is a caller-owned, 16-byte aligned fp32 DEVICE array, prepared once per model (mdm_amd/evaluator.py does it).
+ *
+ * One BiGRU encoder (`gru` + `output_net` of either module, with the `input_emb` in front):
+ *   in_w [H][in_dim], in_b [H]        input_emb
+ *   w_ih [6H][H], b_ih [6H]           weight_ih_l0 then weight_ih_l0_reverse (gate rows r, z, n each), and the biases likewise
+ *   w_hh [2][3H][H], b_hh [2][3H]     weight_hh_l0, weight_hh_l0_reverse
+ *   h0   [2][H]                       the module's learned `hidden`, broadcast over the batch
+ *   o1_w [H][2H], o1_b [H]            output_net.0
+ *   ln_g, ln_b [H]                    output_net.1 (LayerNorm, eps 1e-5); output_net.2 is LeakyReLU(0.2)
+ *   o2_w [out][H], o2_b [out]         output_net.3
+ * H (hidden) must be 256, 512, 768 or 1024; in_dim and out positive multiples of 4. */
+typedef struct mdm_eval_gru {
+  const float* in_w; const float* in_b;
+  const float* w_ih; const float* b_ih;
+  const float* w_hh; const float* b_hh;
+  const float* h0;
+  const float* o1_w; const float* o1_b;
+  const float* ln_g; const float* ln_b;
+  const float* o2_w; const float* o2_b;
+  int32_t in_dim, hidden, out;
+} mdm_eval_gru_t;
+
+/* conv1_w [conv_hidden][4][dim_pose - 4] and conv2_w [latent][4][conv_hidden]: the Conv1d(., ., 4, 2, 1) weights with the tap axis
+ * moved in front of the input channels (k = tap * C_in + c); out_w [latent][latent] is MovementConvEncoder.out_net.
+ * pos_w [word][pos] / in_w of `text` [H][word]: TextEncoderBiGRUCo.pos_emb / input_emb.  motion.in_dim = latent, text.in_dim = word;
+ * conv_hidden, latent and word positive multiples of 4; dim_pose >= 5 (263 HumanML3D, 251 KIT: the last 4 features are not read);
+ * unit_length = 4, the time reduction of the two convolutions (m_lens // unit_length are the recurrent lengths). */
+typedef struct mdm_eval_model {
+  const float* conv1_w; const float* conv1_b;
+  const float* conv2_w; const float* conv2_b;
+  const float* out_w; const float* out_b;
+  const float* pos_w; const float* pos_b;
+  mdm_eval_gru_t motion;
+  mdm_eval_gru_t text;
+  int32_t dim_pose, conv_hidden, latent, word, pos, unit_length;
+} mdm_eval_model_t;
+
+/* Bytes of workspace the larger of the two calls below needs for B sequences of T frames (motion) and L words (text); either of
+ * T and L may be 0 when that call is not made.  0 on a bad argument (mdm_last_error says which).  In floats, per call:
+ *   motion: B (T/2 conv_hidden + T/4 (2 latent + 7 H)) + 5 B H        text: B L (word + 7 H) + 5 B H                              */
+size_t mdm_eval_workspace_bytes(const mdm_eval_model_t* model, int32_t B, int32_t T, int32_t L);
+
+/* motions_dev [B, T, dim_pose] (T >= 4), lens_dev [B] int32 FRAME counts -> out_dev [B, motion.out]: movement encoder, then the
+ * BiGRU over the first lens[b] / unit_length of the T / 4 movement steps of row b, then output_net.  Rows come out in the order
+ * they went in (the reordering by length of the reference's wrapper is the caller's).  max_len: an upper bound of lens[] known to
+ * the host (the recurrence runs max_len / unit_length steps, at most T / 4), or 0 for T.  A row whose length is below unit_length
+ * takes no step and a length beyond T is clamped: the callers refuse both on the host -- the lengths are not read back here.
+ * No device allocation, no synchronisation, every kernel on `stream`: capture-safe. */
+int mdm_eval_motion_embeddings(const mdm_eval_model_t* model, const float* motions_dev, const int32_t* lens_dev, float* out_dev,
+                               int32_t B, int32_t T, int32_t max_len, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* word_embs_dev [B, L, word], pos_ohot_dev [B, L, pos], cap_lens_dev [B] int32 -> out_dev [B, text.out]: input_emb(word_embs +
+ * pos_emb(pos_ohot)), the BiGRU over the first cap_lens[b] words of row b, output_net.  max_len as above, in words. */
+int mdm_eval_text_embeddings(const mdm_eval_model_t* model, const float* word_embs_dev, const float* pos_ohot_dev,
+                             const int32_t* cap_lens_dev, float* out_dev, int32_t B, int32_t L, int32_t max_len,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = [
     "mdm_recover_from_ric", "mdm_workspace_bytes_dec", "mdm_forward_dec", "mdm_workspace_bytes_dec_loop",
     "mdm_sample_loop_dec", "mdm_weights_in_range", "mdm_set_option", "mdm_get_option", "mdm_set_time_add",
     "mdm_rot6d_to_smpl_joints", "mdm_smpl_workspace_bytes", "mdm_smpl_forward",
+    "mdm_eval_workspace_bytes", "mdm_eval_motion_embeddings", "mdm_eval_text_embeddings",
 ]
 # include/mdm_hip_probe.h: exported by the probe build only
 PROBE_SYMBOLS = ["mdm_debug_set", "mdm_debug_get", "mdm_linear_f16f6", "mdm_linear_f16f6_scratch_bytes", "mdm_probe_in_proj"]
@@ -51,6 +52,19 @@ class MdmSmplCall(C.Structure):
     """include/mdm_hip.h mdm_smpl_call_t."""
     _fields_ = [(n, C.c_int32) for n in ("pose_rep", "glob", "translation", "vertstrans", "n_points", "root_point")] + \
                [("point_map", C.POINTER(C.c_int32)), ("glob_rot_mat", C.POINTER(C.c_float)), ("beta1", C.c_float)]
+
+
+class MdmEvalGru(C.Structure):
+    """include/mdm_hip.h mdm_eval_gru_t: one BiGRU encoder (input_emb, gru, output_net) of the evaluator."""
+    _fields_ = [(n, C.c_void_p) for n in ("in_w", "in_b", "w_ih", "b_ih", "w_hh", "b_hh", "h0", "o1_w", "o1_b", "ln_g", "ln_b",
+                                          "o2_w", "o2_b")] + [(n, C.c_int32) for n in ("in_dim", "hidden", "out")]
+
+
+class MdmEvalModel(C.Structure):
+    """include/mdm_hip.h mdm_eval_model_t."""
+    _fields_ = [(n, C.c_void_p) for n in ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "out_w", "out_b", "pos_w", "pos_b")] + \
+               [("motion", MdmEvalGru), ("text", MdmEvalGru)] + \
+               [(n, C.c_int32) for n in ("dim_pose", "conv_hidden", "latent", "word", "pos", "unit_length")]
 
 
 SMPL_POSE_REPS = {"rot6d": 0, "rotvec": 1, "rotmat": 2, "rotquat": 3}      # MDM_SMPL_*: feature counts 6, 3, 9, 4
@@ -133,6 +147,9 @@ class MdmLib:
             "mdm_rot6d_to_smpl_joints": (C.c_int, [vp, vp, P(f32), P(i32), vp, i32, i32, i32, i32, vp]),
             "mdm_smpl_workspace_bytes": (sz, [P(MdmSmplModel), P(MdmSmplCall), i32, i32]),
             "mdm_smpl_forward": (C.c_int, [P(MdmSmplModel), P(MdmSmplCall), vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
+            "mdm_eval_workspace_bytes": (sz, [P(MdmEvalModel), i32, i32, i32]),
+            "mdm_eval_motion_embeddings": (C.c_int, [P(MdmEvalModel), vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+            "mdm_eval_text_embeddings": (C.c_int, [P(MdmEvalModel), vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
         }
         probe_sig = {
             "mdm_debug_set": (C.c_int, [C.c_int, C.c_int]),
