@@ -28,7 +28,9 @@ Workspace carve(const mdm_model* m, int nseq, int T, void* base) {
   const size_t NKT = (S + 31) / 32, SP = 32 * NKT;
   w.qkv = take((size_t)nseq * SP * 3 * D);  // fp32 [M][3D] (f32 mode) or six 16-bit planes of nseq*SP*D (f16x3 mode)
   w.att = take(M * D);
-  w.ffn = take(M * FF);
+  // (at least jf_k floats per row: embed_frames_x3 parks the two pose planes [B*T][jf_k] here, and with ff_size < jf_k = 288 an
+  // unguided forward -- nseq = B -- overran the region into ws.cond, which the same launch reads)
+  w.ffn = take(M * std::max(FF, (size_t)m->jf_k));
   w.cond = take((size_t)nseq * D);
   float* tp = take(M * D);  // two 16-bit planes = one fp32 array's worth of bytes
   w.tokh = reinterpret_cast<p16_t*>(tp);

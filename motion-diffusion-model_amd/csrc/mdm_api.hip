@@ -656,8 +656,14 @@ int mdm_linear(const float* in, const float* w, const float* bias, const float* 
   return launch_linear(nullptr, in, K, w, bias, res, out, M, N, K, act, 0, 1.f, static_cast<hipStream_t>(stream));
 }
 
+// The weight region is sized for N rounded up to whole 256-column tiles although pack_weight_planes_kernel writes the planes of N
+// rounded up to 32 only: every wave of gemm_x3_kernel's last column tile fetches the fragments of its own 32 columns (load_w /
+// aim_w_tile do not look at N), so with N % 256 != 0 the waves past the packed rows read up to 7 blocks of 32 rows behind the lo plane
+// -- values that are never stored, but bytes that must exist.  (In an engine the planes lie inside the constant workspace; here they
+// ended the caller's buffer, and the fetch ran up to 7 * 64 K bytes past it: an illegal address when the buffer ends a mapping.)
 size_t mdm_linear_x3_scratch_bytes(int32_t M, int32_t N, int32_t K) {
-  return align_up((size_t)M * K * 4, 256) + align_up(x3_packed_weight_elems(N, K) * 4, 256);
+  const int32_t n_tiles = (N + 255) / 256 * 256;
+  return align_up((size_t)M * K * 4, 256) + align_up(x3_packed_weight_elems(n_tiles, K) * 4, 256);
 }
 
 int mdm_linear_x3(const float* in, const float* w, const float* bias, const float* res, float* out, int32_t M,
