@@ -13,14 +13,13 @@
 extern "C" {
 #endif
 
-/* Process-global switches; value 0 = production behaviour.  what = 0: split-precision GEMM ablation code (gemm_x3.h ABL);
- * what = 1: mdm_linear_x3 reuses the operand planes already in scratch (kernel-only timing); what = 2: waves per GEMM
- * workgroup, 8 (default: 208/224 x 256 tiles, one workgroup per CU) or 4 (224 x 128 tiles, two per CU); what = 3: attention
- * ablation code; what = 4: mdm_linear_f16f6 on its reference kernel; what = 5: the `f32` mode's encoder GEMMs run unfused on
- * the f16f6 kernel, operands packed per call into a scratch this library allocates itself; what = 6: mdm_linear_x3's plain
- * fp32-out variant runs on the pipelined k-loop (gemm_x3.h PIPE) with ablation codes 0..7. */
+/* Process-global switches; value 0 = production behaviour.  what = 1: mdm_linear_x3 reuses the operand planes already in scratch
+ * (kernel-only timing); what = 3: attention ablation code; what = 4: mdm_linear_f16f6 on its reference kernel; what = 5: the `f32`
+ * mode's encoder GEMMs run unfused on the f16f6 kernel, operands packed per call into a scratch this library allocates itself;
+ * what = 9 / 10 / 11: stamp the value-th launch from now of the gemm_x3s.h / xattn_block.h / selfattn_block.h timeline probes.
+ * what = 0, 2, 6, 8 selected experiments of gemm_x3.h that were removed with their code: MDM_EINVAL. */
 int mdm_debug_set(int what, int value);
-/* Cycle counters of the split-precision GEMM's ABL = 128 build (idx 0..7; idx < 0 resets). */
+/* Timeline stamps: idx 100.. gemm_x3s.h, 200000.. xattn_block.h, 300000.. selfattn_block.h; any other idx: MDM_EINVAL. */
 int mdm_debug_get(int idx, double* out);
 
 /* mdm_linear's contract (res may be null) on the EXPERIMENTAL "f16f6" GEMM (csrc/gemm_f16f6.h: one fp16 MFMA pass + two cross

@@ -122,7 +122,7 @@ int launch_attention_x3_t(const QkvPlanes& qp, const int* lengths, int nseq, int
   // so the number of items is rounded up to a multiple of 8 and surplus workgroups exit
   // persistent workgroups, two per CU (the grid stays a multiple of 16 so that a workgroup keeps its query half)
   const int items = nseq * qp.H, groups = (items + 7) / 8;
-  const int grid = std::min(groups * 16, std::max(16, x3_grid_limit(2) / 16 * 16));
+  const int grid = std::min(groups * 16, std::max(16, 2 * x3_grid_limit() / 16 * 16));
   MDM_LAUNCH(k, dim3(grid), dim3(256), lds, s, qp, lengths, S, D, B, lead, out, oh, ol, items);
   return rt_launch_status();
 }
@@ -277,10 +277,7 @@ int launch_linear_x3(Profiler* pf, X3Operand a, X3Weights w, const float* bias, 
   ProfScope ps(pf, MDM_PROF_LINEAR, 2.0 * M * (double)N * K, s);
   X3Epilogue ep{out, bias, res, res_planes.hi, res_planes.lo, oh, ol, N, scale_cols, col_scale, QkvPlanes{}, 0, 0,
                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1.f, 1, 1, 1};
-#ifdef MDM_PROBES
-  if (g_x3_delay > 1) ep.emb_B = g_x3_delay;
-#endif
-  const int rc = launch_gemm_x3(a, w, ep, M, N, K, act, seq_len, s, g_x3_ablate);
+  const int rc = launch_gemm_x3(a, w, ep, M, N, K, act, seq_len, s);
   if (rc == -2) return fail(MDM_EUNSUPPORTED, "f16x3 linear: unsupported (activation, residual, output) combination");
   return rt_launch_status();
 }

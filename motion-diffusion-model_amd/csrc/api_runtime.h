@@ -7,12 +7,10 @@ namespace {
 
 thread_local std::string g_err;
 #ifdef MDM_PROBES   // libmdm_hip_probe.so only (include/mdm_hip_probe.h): process-global experiment switches
-int g_x3_ablate = 0;        // gemm_x3.h ABL code
 int g_x3_reuse_planes = 0;  // mdm_linear_x3 skips the operand split and reuses the planes in scratch
 int g_f6_reference = 0;     // mdm_linear_f16f6 on the one-wave-per-tile reference kernel
-int g_x3_delay = 0;         // gemm_x3.h, 4-wave form: start delay (x 64 cycles) of every CU's second workgroup
 #else
-constexpr int g_x3_ablate = 0, g_x3_reuse_planes = 0;
+constexpr int g_x3_reuse_planes = 0;
 #endif
 
 int fail(int code, const std::string& msg) {

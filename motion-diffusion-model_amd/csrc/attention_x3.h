@@ -255,9 +255,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
             constexpr int st = u - 2;
             constexpr int younger = 2 * ((7 - st) < 2 ? (7 - st) : 2);
             lds_wait<younger>(kh[st % 3], kl[st % 3]);
-#ifndef MDM_EMU
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            sched_fence();
             if constexpr (ABL & 1) {
 #ifndef MDM_EMU
               asm volatile("" ::"v"(kl[st % 3]), "v"(kh[st % 3]), "v"(qh[st]), "v"(ql[st]));
@@ -267,9 +265,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
               p[t] = mfma_p16(kh[st % 3], ql[st], p[t]);
               p[t] = mfma_p16(kh[st % 3], qh[st], p[t]);
             }
-#ifndef MDM_EMU
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            sched_fence();
           }
         });
 #undef AX_RD_K
@@ -348,9 +344,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
             }
             constexpr int younger = 2 * ((7 - uv) < 2 ? (7 - uv) : 2);
             lds_wait<younger>(vh[uv % 3], vl[uv % 3]);
-#ifndef MDM_EMU
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            sched_fence();
             // a 16-key group wholly past the sequence (only the last one can be) has p == 0 and V^T rows that the in_proj
             // GEMM's 208-row tiles never wrote: skipped, not multiplied
             if constexpr (ABL & 1) {
@@ -362,9 +356,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
               o[dt] = mfma_p16(vh[uv % 3], pl, o[dt]);
               o[dt] = mfma_p16(vh[uv % 3], ph, o[dt]);
             }
-#ifndef MDM_EMU
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            sched_fence();
           }
         });
 #undef AX_RD_V

@@ -583,6 +583,13 @@ __device__ __forceinline__ void wg_barrier_nodrain() {
   __builtin_amdgcn_s_barrier();
 #endif
 }
+// Scheduling fence: hipcc moves no instruction across it (cdna_hip_programming.md rule 18: MFMAs must not be hoisted above a counted
+// wait, an accumulator's MFMAs stay back to back).  The emulator executes in program order.
+__device__ __forceinline__ void sched_fence() {
+#ifndef MDM_EMU
+  __builtin_amdgcn_sched_barrier(0);
+#endif
+}
 // Lanes of one wave exchange data through a wave-private LDS region: the hardware executes a wave's LDS
 // instructions in order, so no barrier instruction is needed -- only the emulator (lanes are fibers) must rendezvous.
 __device__ __forceinline__ void wave_lds_fence() {

@@ -145,7 +145,7 @@ struct DecTail {
 // size measured (B = 32: 544 vs 391 motions/s, B = 64: 660 vs 448; profiles/r04h_dip_planes.md).
 // (sequences of 129 .. 224 tokens, more of them than MDM_OPT_SMALL_GEMM_MAX_SEQS: see decoder_layers_planes)
 inline bool dec_sequence_tiles(const mdm_model* m, int nseq, int S) {
-  return nseq > m->x3s.max_seqs && S > 128 && S <= X3_TM && x3_waves_setting() == 8;
+  return nseq > m->x3s.max_seqs && S > 128 && S <= X3_TM;
 }
 inline bool dec_on_planes(const mdm_model* m, int M, int S, const DecHoist& hz, int B) {
   (void)M;

@@ -24,7 +24,7 @@ int embed_frames_x3(mdm_model* m, const Workspace& ws, const float* x, int B, in
 }
 inline bool use_embed_x3(const mdm_model* m, int T) {
   // (longer sequences: the row-tile form of the same GEMM where it exists -- 263 features -- else the fp32-operand embedding below)
-  return m->precision == MDM_PREC_F16X3 && x3_waves_setting() == 8 &&
+  return m->precision == MDM_PREC_F16X3 &&
          (T + 1 <= X3_TM || (use_small_gemm(m, 1, T + 1) && m->jf_k == 288));
 }
 
@@ -60,7 +60,7 @@ int encoder(mdm_model* m, const Workspace& ws, int nseq, int B, int S, const int
   Profiler* pf = &m->prof;
   const int D = m->cfg.latent_dim, FF = m->cfg.ff_size, H = m->cfg.num_heads, M = nseq * S;
   const float qscale = 1.0f / sqrtf((float)(D / H));
-  if (m->precision == MDM_PREC_F16X3 && m->lnfold && x3_waves_setting() == 8 && (S <= X3_TM || use_small_gemm(m, nseq, S))) {
+  if (m->precision == MDM_PREC_F16X3 && m->lnfold && (S <= X3_TM || use_small_gemm(m, nseq, S))) {
     // No LayerNorm kernels: xb = tokh|tokl holds the layer input / the post-FFN PRE-norm sum, xa the post-attention
     // pre-norm sum, each with per-row partial (sum, sum^2) written by its producer; consumers fold the normalisation
     // (gemm_x3.h X3Epilogue).  Layer 0's input (the embedding) is not normalised: plain in_proj, plain residual.
@@ -80,8 +80,8 @@ int encoder(mdm_model* m, const Workspace& ws, int nseq, int B, int S, const int
     // measured in round 4: attention 2 x 59.4 us against 111.5, in_proj 2 x 132.1 against 257.3, whole loop 1.0-1.5 % SLOWER on the
     // same box -- profiles/r04i_halves.md -- and removed.)
     // (Running the batch as TWO concurrent half-batch chains on two streams, each GEMM launch on half the CUs, so that one chain's
-    // epilogue store bursts fall into the other's k-loops: round 5, probe-library hooks MDM_CHAIN_FREE / MDM_X3_GRID_DIV,
-    // lab/probes/two_chains.py -- 3.5 % SLOWER, bit-identical results: profiles/r05l_two_chains.md.)
+    // epilogue store bursts fall into the other's k-loops: round 5, probe-library hook MDM_CHAIN_FREE and a per-launch grid
+    // divider that has since been removed, lab/probes/two_chains.py -- 3.5 % SLOWER, bit-identical results: profiles/r05l_two_chains.md.)
     for (int l = 0; l < m->cfg.num_layers; ++l) {
       const mdm_model::LayerPlanes& P = m->planes[l];
       const mdm_model::LayerFold& F = m->fold[l];
@@ -164,7 +164,7 @@ int outproj_x3(mdm_model* m, const Workspace& ws, int nseq, int B, int T, const 
   const int D = m->cfg.latent_dim, S = T + 1, ldo = m->jf_out;
   float* out_tok = ws.qkv;
   ProfScope ps(&m->prof, MDM_PROF_OUTPROJ, 2.0 * nseq * T * (double)D * m->jf, s);
-  if (m->lnfold && x3_waves_setting() == 8 && (S <= X3_TM || use_small_gemm(m, nseq, S))) {   // the final LayerNorm is folded into this GEMM
+  if (m->lnfold && (S <= X3_TM || use_small_gemm(m, nseq, S))) {   // the final LayerNorm is folded into this GEMM
     LnArgs a; a.astat = ws.stat2; a.colsum = m->c_out; a.inv_dim = 1.0f / (float)D;
     a.small = use_small_gemm(m, nseq, S);            // (the same decision the encoder took: who wrote stat2)
     a.shape = x3s_shape(m->x3s, nseq);

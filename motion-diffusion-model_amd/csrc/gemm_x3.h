@@ -17,27 +17,24 @@
 // global_load_dwordx4 -- weights never pass through LDS (a wave's 32 output columns are private to it, so staging them
 // in LDS bought nothing and cost an LDS-DMA write plus an LDS read per byte).
 //
-// Instruction shape (round 7).  The product's pipelined loop (PIPE, 208-row tiles) runs the whole tile on v_mfma_f32_16x16x32_f16:
-// per wave 13 row slices of 16 x 2 column halves of f32x4 accumulators (104 VGPRs), the A fragment of a slice one ds_read_b128 per
-// plane, the W fragments read from the same fragment-ordered planes through a per-lane remap (M16 in the kernel below).  Under the
-// power limit that shape delivers more FLOP/s than 32x32x16 at equal cycles per FLOP: in_proj 251 -> 232 us per launch, headline
-// +8.4 % same box (profiles/r07a_m16.md).  The step-synchronous loop (InputProcess) stays on 32x32x16, with its last 16-row slice on
-// 16x16x32; the round-6 pipelined form (32x32x16) remains in the probe library (MDM_X3_M32=1).
-//
-// Machine mapping (gfx950).  WAVES waves per PERSISTENT workgroup, each wave owning 32 output columns x all 7 row
-// sub-tiles of the tile (7 accumulators = 112 VGPRs; 104 on 208-row tiles):
-//     WAVES = 8 (default)  224 x 256 tiles, one workgroup per CU (66-97 KB of LDS, <= 256 VGPRs)
-//     WAVES = 4            224 x 128 tiles, two independent workgroups per CU, which hide each other's barriers, LDS-DMA
-//                          latency and epilogues -- and re-read the activation panels twice as often from L2.
-// Whole-bench A/B on one box: 307 vs 302 motions/s.  The two shapes, four instruction schedules and two wave-priority
-// schemes all measure within 0.1-3 % of each other: while this kernel runs the chip sits at its power limit (zero-filled
-// operands: +16-22 %), and the costs of the parts add up instead of overlapping -- MFMA-only 141 us + epilogue stores
-// 25-40 + fragment reads / barriers 18 + loads 32 = 230 us for in_proj (profiles/r01c_final.md).  What pays is less
-// work and fewer bytes.
-//   * the row extent of a tile is a whole number of token sequences (S = 197 -> one sequence per tile), so the headline
-//     shape (256 sequences, N in {512, 1024, 1536}) gives every CU exactly N/256 equal tiles;
-//   * A tile: global -> LDS by global_load_lds_dwordx4, BK = 32, two stages of Ah|Al [224][32] = 28 KB; the pieces a
-//     wave issues per step ride BETWEEN the MFMA units; the stream has its own (tile, k) cursor one step ahead and
+// Machine mapping (gfx950).  One PERSISTENT workgroup of eight waves per CU works on 256-column tiles whose row extent is a whole
+// number of token sequences (S = 197 -> one sequence per tile), so the headline shape (256 sequences, N in {512, 1024, 1536}) gives
+// every CU exactly N/256 equal tiles; each wave owns 32 output columns x all rows of the tile.  Two k-loops exist:
+//   * the PIPELINED loop (X3_PIPE; 208-row tiles, an even number of 32-deep k steps: every encoder GEMM but InputProcess) runs
+//     the whole tile on v_mfma_f32_16x16x32_f16: per wave 13 row slices of 16 x 2 column halves of f32x4 accumulators (104 VGPRs),
+//     the A fragment of a slice one ds_read_b128 per plane, the W fragments read from the same fragment-ordered planes through a
+//     per-lane remap.  Every stream runs AHEAD of the matrix work: A in four LDS stages (A(g+3) is issued during step g; each wave
+//     retires its own pieces of A(g+1) with a COUNTED vmcnt in the middle of the step, then one bare s_barrier -- no drain --
+//     makes them visible), W in four register slots (two column halves x step parity) refilled in place for step g+2, the fragment reads two elements
+//     ahead across step and stage boundaries: the pipeline never restarts inside a tile (details at the k-loop);
+//   * the STEP-SYNCHRONOUS loop (InputProcess, K = 288: nine steps; odd step counts; 224-row tiles) runs on v_mfma_f32_32x32x16_f16,
+//     7 row sub-tiles of 32 (112 VGPRs) or, on 208-row tiles (X3_T16), six plus one 16-row sub-tile on 16x16x32: two LDS stages,
+//     A(g+1) and W(g+1) fetched during step g, every step closed by vmcnt(0) and one barrier.
+// While this kernel runs the chip sits at its power limit (zero-filled operands: +16-22 %) and the costs of the parts add up
+// instead of overlapping -- MFMA-only 141 us + epilogue stores 25-40 + fragment reads / barriers 18 + loads 32 = 230 us for
+// in_proj (profiles/r01c_final.md).  What pays is less work and fewer bytes.
+//   * A tile: global -> LDS by global_load_lds_dwordx4, BK = 32, stages of Ah|Al [224][32] = 28 KB; the pieces a
+//     wave issues per step ride BETWEEN the MFMA units; the stream has its own (tile, k) cursor ahead of the matrix work and
 //     rolls over into the workgroup's next tile, so the pipeline never drains at a tile boundary;
 //   * LDS image: row-major, 64-byte rows, 16-byte chunk index XOR-swizzled with x3_swz((row>>2)&3), x3_swz = (0, 2, 3, 1) (below):
 //     one image whose ds_read_b128 lane groups are conflict-free on the 16x16x32 read pattern AND on both 32x32x16 ones (rounds
@@ -45,13 +42,19 @@
 //     LDS-DMA writes lane-linearly, so the swizzle is applied to the per-lane SOURCE address and to the reads
 //     (cdna_hip_programming.md rule 21).  Fragment reads are issued through untracked inline-asm ds_reads retired by
 //     counted lgkmcnt waits (common.h lds_read16): hipcc only ever emits lgkmcnt(0) beside an LDS-DMA;
-//   * W fragments for step g+1 are fetched into registers during step g (plain loads, waited with the step's vmcnt);
 //   * XCD-aware tile order keeps the workgroups that share an activation row panel on one XCD's L2.
+//
+// Retired forms (measured, written up and removed from this file; lab/README.md names the last commit that has them):
+//   * four waves on 224 x 128 tiles, two workgroups per CU: 302 vs 307 motions/s (profiles/r01c_final.md), and the start delay
+//     that ran a CU's two workgroups in anti-phase: 0.0 % (profiles/r05h_dephase.md);
+//   * four waves x 64 columns, one wave per SIMD ("wide"): 12-18 % slower per launch, in_proj spilled (profiles/r04d_wide.md);
+//   * the pipelined loop on 32x32x16 MFMAs: in_proj 251 vs 232 us per launch, headline -8.4 % (profiles/r07a_m16.md);
+//   * the timing ablations and cycle counters of rounds 1-3 (profiles/r01c_final.md, profiles/r03c_ab.md);
+//   * the epilogue that reads its patch one round ahead: neutral here (profiles/r05j_epilogue_ahead.md); gemm_x3s.h keeps its own.
 #pragma once
 #include "attention_x3.h"  // QkvPlanes: the in_proj epilogue writes the attention kernel's operand planes
 #include "common.h"
 #include "gemm_f32.h"  // ACT_* enums
-#include <cstdlib>
 
 namespace mdm {
 
@@ -68,75 +71,41 @@ constexpr int X3_TM = 224, X3_BK = 32;
 // f = (0, 2, 3, 1) is one of the eight permutations that are 1-way on all three patterns (tests/test_host_lds_swizzle.py).
 __host__ __device__ constexpr int x3_swz(int q) { return (((q ^ (q >> 1)) & 1) << 1) | (q >> 1); }
 static_assert(x3_swz(0) == 0 && x3_swz(1) == 2 && x3_swz(2) == 3 && x3_swz(3) == 1, "A-stage swizzle permutation");
-// WAVES waves per workgroup, each owning 32 output columns: 4 -> 224x128 tiles, two workgroups per CU;
-//                                                            8 -> 224x256 tiles, one workgroup per CU (half the
-//                                                                 activation re-reads from L2, waves in lock-step)
-constexpr int x3_tn(int waves) { return 32 * waves; }
+constexpr int X3_NWAVE = 8;                                      // waves per workgroup, each owning 32 output columns
+constexpr int X3_TN = 32 * X3_NWAVE;                             // 224 x 256 tiles, one workgroup per CU
 constexpr int X3_MSUB = X3_TM / 32;                              // 7 row sub-tiles
 constexpr int X3_A_BYTES = X3_TM * X3_BK * 2;                    // one A plane tile: 14336
 constexpr int X3_A_STAGE = 2 * X3_A_BYTES;                       // Ah|Al: 28672
 constexpr int X3_A_RING = 2;                                     // stages of the step-synchronous k-loop
 constexpr int X3_PIPE_RING = 4;                                  // stages of the pipelined k-loop (PIPE): A runs 3 steps ahead
-// -DMDM_X3_EPI_AHEAD=1: the epilogue reads round j+1's patch BEFORE it finishes round j (a wave's LDS operations execute in order, so the
-// one patch is enough: read j+1, then write j+2 behind it) -- the patch round trip is two rounds of VALU work away from its use
-// instead of one wait away (0-4 more VGPRs).  Measured NEUTRAL on the headline (GEMM class 291.9, 291.5 vs 291.2, 292.7 ms per loop,
-// profiles/r05j_epilogue_ahead.md): this kernel's epilogue does not wait for its 28 LDS round trips -- which also closes the 16-row-round
-// variant of VERDICT r04 -- so the switch stays off; gemm_x3s.h's twin gains 0.3-0.5 % and is on
-#ifndef MDM_X3_EPI_AHEAD
-#define MDM_X3_EPI_AHEAD 0
-#endif
-constexpr bool X3_EPI_AHEAD = MDM_X3_EPI_AHEAD != 0;
-// -DMDM_X3_PIPE_BADWAIT: a deliberately too lenient middle-of-step wait -- the check that the emulator's LATE mode
-// (tests/emu/hip_emu.h) really catches a wrong count (profiles/r03a_pipe_emulator.md); never defined in a product build
-#ifdef MDM_X3_PIPE_BADWAIT
-constexpr int X3P_MID_SLACK = 8;
-#else
-constexpr int X3P_MID_SLACK = 0;
-#endif
-// Counted vmcnt waits of the pipelined loop.  ORDERED: the queue retires in issue order across both kinds of operation it
-// holds (LDS-DMA pieces of A, VGPR loads of W) -- the count is the number of YOUNGER operations of either kind.  STRICT
-// (-DMDM_X3_PIPE_STRICT): only operations of the SAME kind are assumed to retire in order -- the count is the number of younger
-// operations of the awaited kind alone, i.e. the wait also holds if every operation of the other kind has already retired.
-#if defined(MDM_X3_PIPE_WDRAIN)     // (bisection build: both waits drain the whole queue)
-constexpr int X3P_WAIT_WS = 0, X3P_WAIT_MID = 0;
-#elif defined(MDM_X3_PIPE_STRICT)
-constexpr int X3P_WAIT_WS = 6, X3P_WAIT_MID = 3;
-#else
-constexpr int X3P_WAIT_WS = 12, X3P_WAIT_MID = 7;
-#endif
-// ... and of the 16x16x32 form (M16), whose queue holds per step and wave  A(g+3) x nA | W(g+2) x 4  (nA >= 3):
-//   step start, slots W(g):  younger = A(g+2) + W(g+1) = 3 + 4                      (STRICT: W(g+1) = 4)
-//   middle, own A(g+1):      younger = W(g) + A(g+2) + W(g+1) = 4 + 3 + 4            (STRICT: A(g+2) = 3)
-// (ORDERED, the start-of-step wait already retires A(g+1), which is older than W(g); the middle wait states the need)
-#if defined(MDM_X3_PIPE_WDRAIN)
-constexpr int X3M_WAIT_WS = 0, X3M_WAIT_MID = 0;
-#elif defined(MDM_X3_PIPE_STRICT)
-constexpr int X3M_WAIT_WS = 4, X3M_WAIT_MID = 3;
-#else
+// Counted vmcnt waits of the pipelined loop, whose queue holds per step and wave  A(g+3) x nA | W(g+2) x 4  (nA >= 3: the 26 groups
+// of a 208-row tile dealt to eight waves).  The queue retires in issue order across both kinds of operation it holds (LDS-DMA pieces
+// of A, VGPR loads of W), so a count is the number of YOUNGER operations of either kind:
+//   step start, slots W(g):  younger = A(g+2) + W(g+1) = 3 + 4
+//   middle, own A(g+1):      younger = W(g) + A(g+2) + W(g+1) = 4 + 3 + 4
+// (the start-of-step wait already retires A(g+1), which is older than W(g); the middle wait states the need).  If only operations
+// of the SAME kind were assumed to retire in order, the counts would be 4 (W(g+1)) and 3 (A(g+2)).
 constexpr int X3M_WAIT_WS = 7, X3M_WAIT_MID = 11;
-#endif
 constexpr int x3_patch_base(int ring) { return ring * X3_A_STAGE; }   // 57344 (2 stages) / 114688 (4)
 constexpr int X3_PATCH_BYTES = 8 * 32 * 4;                       // per wave: 8 rows x 32 columns fp32
 constexpr int X3_TAB_BYTES = X3_TM * 8;                          // one (mean, rstd) table of the tile's rows
 // LDS after the patches: the (mean, rstd) table of the tile's rows (FOLD or RES == 3: a kernel has one of them) and the
 // raw partial sums it is built from (<= 4 partials per row: 7 KB, the LDS-DMA lands whole KBs), both double-buffered by
 // tile parity, then the per-wave partial sums of OSTAT
-constexpr int x3_tab_base(int waves, int ring = X3_A_RING) { return x3_patch_base(ring) + waves * X3_PATCH_BYTES; }
+constexpr int x3_tab_base(int ring) { return x3_patch_base(ring) + X3_NWAVE * X3_PATCH_BYTES; }
 constexpr int X3_RAW_BYTES = 7 * 1024;
-constexpr int x3_raw_base(int waves, int ring = X3_A_RING) { return x3_tab_base(waves, ring) + 2 * X3_TAB_BYTES; }      // tables: 2 (tile parity)
-constexpr int x3_part_base(int waves, int ring = X3_A_RING) { return x3_raw_base(waves, ring) + 2 * X3_RAW_BYTES; }    // raw partials: 2 (parity)
+constexpr int x3_raw_base(int ring) { return x3_tab_base(ring) + 2 * X3_TAB_BYTES; }      // tables: 2 (tile parity)
+constexpr int x3_part_base(int ring) { return x3_raw_base(ring) + 2 * X3_RAW_BYTES; }    // raw partials: 2 (parity)
 // last: the epilogue's per-column vectors of the tile (bias, folded column sums, residual gamma, beta: 4 x 256 floats),
 // fetched by LDS-DMA one tile ahead, double-buffered by tile parity
 constexpr int X3_CVEC_BYTES = 4 * 1024;
-constexpr int x3_cvec_base(int waves, bool ln, int ring = X3_A_RING) {
-  return ln ? x3_part_base(waves, ring) + waves * X3_TAB_BYTES : x3_tab_base(waves, ring);
-}
-// 69632 (4 waves) / 73728 (8); with the LayerNorm tables 95232 (8); the 4-stage pipelined form 131072 / 152576
-constexpr int x3_lds_bytes(int waves, bool ln, int ring = X3_A_RING) {
-  return x3_cvec_base(waves, ln, ring) + 2 * X3_CVEC_BYTES;
-}
+constexpr int x3_cvec_base(bool ln, int ring) { return ln ? x3_part_base(ring) + X3_NWAVE * X3_TAB_BYTES : x3_tab_base(ring); }
+constexpr int x3_lds_bytes(bool ln, int ring) { return x3_cvec_base(ln, ring) + 2 * X3_CVEC_BYTES; }
+// two stages: 73728, with the LayerNorm tables 105984; four stages (pipelined): 131072 / 163328 of the CU's 163840
+static_assert(x3_lds_bytes(false, X3_A_RING) == 73728 && x3_lds_bytes(true, X3_A_RING) == 105984, "LDS of the step-synchronous form");
+static_assert(x3_lds_bytes(false, X3_PIPE_RING) == 131072 && x3_lds_bytes(true, X3_PIPE_RING) == 163328, "LDS of the pipelined form");
 constexpr int X3_A_GROUPS = X3_A_STAGE / 1024;                   // 28 LDS-DMA wave-instructions per stage
-constexpr int x3_a_pieces(int waves) { return (X3_A_GROUPS + waves - 1) / waves; }  // 7 (4 waves) / 4 (8 waves)
+constexpr int X3_A_PIECES = (X3_A_GROUPS + X3_NWAVE - 1) / X3_NWAVE;   // 4 per wave and step
 
 struct X3Operand {   // activations: [rows][K] planes
   const p16_t* hi;
@@ -252,27 +221,28 @@ constexpr int x3_res_younger_rounds(int t, int rr, bool t16) {
   return n;
 }
 
-// ABL & 128 (timing experiment): cycles (s_memtime) wave 0 of every workgroup spends [0] in the end-of-step vmcnt(0) of a
-// tile's FIRST k step -- which also drains the previous tile's epilogue stores --, [1] in the same wait of all other steps,
-// [2] in whole k-loops, [3] in whole epilogues; [4] tiles, [5] k steps.  Read with mdm_debug_get.
-#if !defined(MDM_EMU) && defined(MDM_PROBES)
-#define MDM_X3_DBG 1
-__device__ unsigned long long g_x3_dbg[8];
-__device__ __forceinline__ unsigned long long x3_now() { return __builtin_readcyclecounter(); }
-#endif
-
 // The A load stream: which tile of this workgroup and which k step it fetches next, and the per-lane source element
-// offsets of the wave's seven LDS-DMA pieces for that tile.
-template <int PIECES>
+// offsets of the wave's LDS-DMA pieces for that tile.
 struct X3Cursor {
   int v;        // virtual tile id (blockIdx.x + j * gridDim.x)
   int k;        // next k step
-  uint32_t off[PIECES];
+  uint32_t off[X3_A_PIECES];
 };
 
-// RES: 0 = no residual, 1 = fp32 residual, 2 = residual held as 16-bit hi/lo planes.
-// ABL (profiling experiments only, 0 in production): 1 = no epilogue stores, 2 = no loads after the prologue,
-// 4 = no MFMAs, 8 = loads issued but not waited for, 16 / 32 / 64 / 256 = timing probes described where they are used.
+// The kernel's options: ACT (gemm_f32.h ACT_*), RES and one word of X3_* flags.
+// RES: 0 = no residual, 1 = fp32 residual, 2 = residual held as 16-bit hi/lo planes, 3 = LayerNorm of such planes.
+enum : unsigned {
+  X3_OUT_F32 = 1u << 0,      // output: fp32 [M][ld]
+  X3_OUT_PLANES = 1u << 1,   //         hi/lo planes [M][ld]
+  X3_OUT_QKV = 1u << 2,      //         the attention kernel's operand planes (in_proj)
+  X3_FOLD = 1u << 3,         // the LayerNorm of the A rows is folded into this GEMM
+  X3_OSTAT = 1u << 4,        // writes the partial row statistics of its output
+  X3_EMBED = 1u << 5,        // InputProcess: positional rows, planes to the token rows of every branch
+  X3_T16 = 1u << 6,          // 208-row tile
+  X3_F6 = 1u << 7,           // the f16f6 arithmetic on the step-synchronous loop
+  X3_PIPE = 1u << 8,         // the pipelined k-loop on 16x16x32 MFMAs
+  X3_PAIR = 1u << 9,         // one tile serves both guidance branches of a sample
+};
 // FOLD / OSTAT / RES == 3: LayerNorm folded into the GEMMs (X3Epilogue).
 // T16: the tile is 208 rows -- six 32-row sub-tiles plus ONE 16-row sub-tile (rows 192-207) on v_mfma_f32_16x16x32_bf16 --
 // for row extents <= 208 (S = 197: 11 pad rows instead of 27, i.e. 6.5 of 7 units of matrix work and 13 of 14 A groups).
@@ -281,35 +251,34 @@ struct X3Cursor {
 // F6: the k-loop runs the "f16f6" arithmetic of gemm_f16f6.h on the same skeleton -- plane 0 holds fp16 values, plane 1 the MX-FP6
 // records, the weight planes come from pack_weight_f16f6_kernel; units are ordered sub-tile-major so that a sub-tile's two
 // 16-byte record reads (k sub-steps 0 and 1) meet in ONE scaled MFMA; 2 + 1 MFMAs per sub-tile and step instead of 6.
-// NCB (round 4, "wide" form): 32-column blocks per wave.  NCB = 2 with WAVES = 4 is the one-wave-per-SIMD arrangement of the SAME
-// 208 x 256 tile: four waves x 64 columns, ONE workgroup per CU, up to 512 registers per lane (accumulators 208, W slots 64), every
-// A fragment read from LDS feeds two column blocks -- half the LDS fragment traffic and half the rendezvous partners of the
-// 8-wave form.  Pipelined loop only.
-// M16 (round 7, the product form): the pipelined 8-wave loop with the WHOLE 208-row tile on v_mfma_f32_16x16x32_f16 -- 13 row
-// slices x 2 column halves of f32x4 accumulators per wave (see the k-loop below); the 32x32x16 form (M16 = false) is compiled into
-// the probe library only.
+// PIPE (round 7): the pipelined loop with the WHOLE 208-row tile on v_mfma_f32_16x16x32_f16 -- 13 row slices x 2 column halves of
+// f32x4 accumulators per wave (see the k-loop below).
 // PAIR (round 8, layer 0's in_proj under guidance): sequences b and pair_B + b of the 2 pair_B the planes hold differ only in token 0
 // (the condition token; the frame tokens are written once to both by the embedding GEMM), so ONE tile serves both: tile rows
 // 0 .. S-1 are sequence b, tile row S -- a pad row of the 208-row tile, S <= 207 -- is loaded from token 0 of sequence pair_B + b.
 // The epilogue writes row 0 to sequence b, rows 1 .. S-1 to both and row S to token 0 of sequence pair_B + b: every Q / K / V^T
 // element keeps its products and their order, a row's position in the tile does not enter them.  M, the grid and the k-loop (its
 // stages, piece dealing and counted waits) are those of a pair_B-sequence launch; only one lane's source offset per plane differs.
-template <int WAVES, int ACT, int RES, bool OUT_F32, bool OUT_PLANES, bool OUT_QKV, int ABL, bool FOLD = false,
-          bool OSTAT = false, bool EMBED = false, bool T16 = false, bool F6 = false, bool PIPE = false, int NCB = 1,
-          bool M16 = false, bool PAIR = false>
-__global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X3Operand A, X3Weights W, X3Epilogue ep, int M, int N,
-                                                                     int K, int rows_per_tile, int tiles_n, int total) {
+template <int ACT, int RES, unsigned FLAGS>
+__global__ __launch_bounds__(64 * X3_NWAVE, 2) void gemm_x3_kernel(X3Operand A, X3Weights W, X3Epilogue ep, int M, int N, int K,
+                                                                   int rows_per_tile, int tiles_n, int total) {
   MDM_DYN_SMEM(unsigned char, lds);
-  static_assert(!PIPE || (T16 && (WAVES == 8 || (WAVES == 4 && NCB == 2)) && !F6), "the pipelined k-loop exists for 208-row (T16), 256-column tiles");
-  static_assert(NCB == 1 || (NCB == 2 && PIPE && WAVES == 4), "two column blocks per wave: the pipelined 4-wave form only");
-  static_assert(!M16 || (PIPE && WAVES == 8 && NCB == 1 && ABL == 0), "the 16x16x32 form: pipelined, 8 waves, no ablations");
-  static_assert(!PAIR || (M16 && OUT_QKV && !FOLD), "the paired tile: layer 0's in_proj (no folded LayerNorm) on the 16x16x32 form");
+  constexpr bool OUT_F32 = (FLAGS & X3_OUT_F32) != 0, OUT_PLANES = (FLAGS & X3_OUT_PLANES) != 0, OUT_QKV = (FLAGS & X3_OUT_QKV) != 0;
+  constexpr bool FOLD = (FLAGS & X3_FOLD) != 0, OSTAT = (FLAGS & X3_OSTAT) != 0, EMBED = (FLAGS & X3_EMBED) != 0;
+  constexpr bool T16 = (FLAGS & X3_T16) != 0, F6 = (FLAGS & X3_F6) != 0, PIPE = (FLAGS & X3_PIPE) != 0, PAIR = (FLAGS & X3_PAIR) != 0;
+  static_assert(FLAGS < (X3_PAIR << 1), "unknown flag");
+  static_assert((int)OUT_F32 + (int)OUT_PLANES + (int)OUT_QKV == 1, "exactly one output form");
+  static_assert(RES >= 0 && RES <= 3 && !(OUT_QKV && RES != 0), "in_proj has no residual");
+  static_assert(!(FOLD && RES == 3), "one (mean, rstd) table: of the A rows or of the residual rows");
+  static_assert(!OSTAT || OUT_PLANES, "row statistics are written next to the planes they describe");
+  static_assert(!EMBED || (OUT_PLANES && RES == 1 && !PIPE), "InputProcess: fp32 positional rows, planes out, step-synchronous loop");
+  static_assert(!PIPE || (T16 && !F6), "the pipelined k-loop exists for 208-row (T16) tiles");
+  static_assert(!F6 || (!T16 && OUT_F32 && !FOLD && !OSTAT), "the f16f6 k-loop: 224-row tiles, plain fp32-out epilogues");
+  static_assert(!PAIR || (PIPE && OUT_QKV && !FOLD), "the paired tile: layer 0's in_proj (no folded LayerNorm) on the pipelined loop");
   constexpr int RINGN = PIPE ? X3_PIPE_RING : X3_A_RING;   // A stages in LDS
-  constexpr int NBLK = WAVES * NCB;                        // 32-column blocks of a tile (the LDS layout is per block)
-  constexpr int X3_WAVES = WAVES, X3_TN = 32 * NBLK, X3_A_PIECES = x3_a_pieces(WAVES);
   constexpr int NT32 = T16 ? X3_MSUB - 1 : X3_MSUB;     // 32-row sub-tiles
   constexpr int NROUNDS = 4 * NT32 + (T16 ? 2 : 0);     // epilogue rounds of 8 rows
-  using Cursor = X3Cursor<X3_A_PIECES>;
+  using Cursor = X3Cursor;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -330,7 +299,7 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
   };
 
   // ---- LDS-DMA sources.  A stage image = 28 groups of 1 KB (16 rows x 64 B): groups 0-13 Ah, 14-27 Al.  Wave w issues
-  // groups w, w+4, ..., w+24.  Lane -> (row = lane>>2, stored chunk = lane&3); the logical k-chunk it fetches is
+  // groups w, w+8, w+16, w+24.  Lane -> (row = lane>>2, stored chunk = lane&3); the logical k-chunk it fetches is
   // stored ^ x3_swz((row>>2)&3) = (lane&3) ^ x3_swz((lane>>4)&3).  Rows past the tile / matrix are clamped (never stored).
   const int schunk = (lane & 3) ^ x3_swz((lane >> 4) & 3);
   auto aim_a = [&](Cursor& c) {
@@ -340,31 +309,25 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
     for (int i = 0; i < X3_A_PIECES; ++i) {
       // PIPE: the 26 groups a 208-row tile reads (13 per plane) are dealt round-robin: piece j = wid + 8 i -> group j (hi) /
       // j + 1 (lo, stage groups 14..26); waves 0 and 1 issue four pieces per step, the others three
-      const int jj = min(wid + X3_WAVES * i, 25);
-      const int q = PIPE ? (jj < 13 ? jj : jj + 1) : min(wid + X3_WAVES * i, X3_A_GROUPS - 1);
+      const int jj = min(wid + X3_NWAVE * i, 25);
+      const int q = PIPE ? (jj < 13 ? jj : jj + 1) : min(wid + X3_NWAVE * i, X3_A_GROUPS - 1);
       const int ga = (q < 14) ? q : q - 14;
       int arow = min(m0 + ga * 16 + (lane >> 2), M - 1);
       if constexpr (PAIR) {   // tile row S: token 0 of the other branch's sequence (rows_per_tile == S, M == pair_B * S)
         if (ga * 16 + (lane >> 2) == rows_per_tile) arow = m0 + M;
       }
-      if constexpr ((ABL & 16) != 0) {
-        // timing experiment: a k-BLOCKED plane layout ([row/16][k/32][16 rows][32 k]) would make every piece one
-        // contiguous KB; the data fetched here is wrong, only the address pattern is representative
-        c.off[i] = (uint32_t)(arow >> 4) * (uint32_t)(K / 32) * 512u + (uint32_t)(arow & 15) * 32u + schunk * 8;
-      } else {
-        c.off[i] = (uint32_t)arow * (uint32_t)K + schunk * 8;
-      }
+      c.off[i] = (uint32_t)arow * (uint32_t)K + schunk * 8;
     }
   };
   auto piece_a = [&](const Cursor& c, int i, int buf) {
     if constexpr (PIPE) {
-      const int j = wid + X3_WAVES * i;
+      const int j = wid + X3_NWAVE * i;
       const int q = j < 13 ? j : j + 1;
       if (j < 26) glds16(((q < 14) ? A.hi : A.lo) + c.off[i] + c.k * X3_BK, lds + buf * X3_A_STAGE + q * 1024);
     } else {
-      const int q = wid + X3_WAVES * i;
+      const int q = wid + X3_NWAVE * i;
       if (q < X3_A_GROUPS && !(T16 && (q == 13 || q == 27)))   // T16: rows 208-223 of the stage are never read
-        glds16(((q < 14) ? A.hi : A.lo) + c.off[i] + c.k * ((ABL & 16) ? 512 : X3_BK), lds + buf * X3_A_STAGE + q * 1024);
+        glds16(((q < 14) ? A.hi : A.lo) + c.off[i] + c.k * X3_BK, lds + buf * X3_A_STAGE + q * 1024);
     }
   };
   // past its last tile the stream simply re-fetches that tile (one wasted stage per workgroup): no "anything left to
@@ -401,17 +364,6 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
 
   int v = (int)blockIdx.x;
   if (v >= total) return;
-#if defined(MDM_PROBES) && !defined(MDM_EMU)
-  // (probe build, mdm_debug_set(8, d): the SECOND workgroup of every CU -- the upper half of the grid in dispatch order -- starts
-  // d * 64 cycles late, so that the two 4-wave workgroups of a CU run their k-loops and epilogues in anti-phase:
-  // tools/gemm_dephase_probe.py, profiles/r04b_ab.md)
-  if constexpr (WAVES == 4 && !EMBED) {
-    if (ep.emb_B > 1 && (int)blockIdx.x >= gstride / 2) {
-      const unsigned long long t0 = __builtin_readcyclecounter();
-      while (__builtin_readcyclecounter() - t0 < (unsigned long long)ep.emb_B * 64ULL) __builtin_amdgcn_s_sleep(8);
-    }
-  }
-#endif
   Cursor ca{v, 0, {}};
   aim_a(ca);
   int wv = v, wkk = 0;   // the W stream's (tile, k): one step ahead of the MFMAs, like the A stream
@@ -424,7 +376,7 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
   auto stats_dma = [&](int m0s, int par) {
     const float* st = FOLD ? ep.astat : ep.rstat;
     const int npieces = (X3_TM * ep.stat_parts * 8 + 1023) / 1024;
-    for (int pc = wid; pc < npieces; pc += X3_WAVES) {      // (<= 7 pieces; four waves take two)
+    for (int pc = wid; pc < npieces; pc += X3_NWAVE) {      // (<= 7 pieces)
       // A 16-byte unit keeps its place in the table (unit u of the tile = floats 4u .. 4u+3 behind the tile's first row) as long
       // as it holds any float of the matrix; units entirely past it read a valid address instead.  With an odd number of
       // partials per row (D = 256, 768) a tile that starts on an odd row is only 8-byte aligned and its last unit may straddle
@@ -434,7 +386,7 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
       const long long total_f = (long long)M * ep.stat_parts * 2;
       long long fo = (long long)m0s * ep.stat_parts * 2 + 4LL * (64 * pc + lane);
       if (fo >= total_f) fo = 0;                                       // rows past the matrix: any valid address
-      glds16(st + fo, lds + x3_raw_base(NBLK, RINGN) + par * X3_RAW_BYTES + pc * 1024);
+      glds16(st + fo, lds + x3_raw_base(RINGN) + par * X3_RAW_BYTES + pc * 1024);
     }
   };
   // the epilogue's per-column vectors of the tile starting at column n0c -> LDS buffer `par`: wave 0 bias, wave 1 folded
@@ -446,7 +398,7 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
     if (wid == 0) src = ep.bias;
     if constexpr (FOLD) { if (wid == 1) src = ep.colsum; }
     if constexpr (RES == 3) { if (wid == 2) src = ep.rgamma; if (wid == 3) src = ep.rbeta; }
-    if (src != nullptr) glds16(src + min(n0c + 4 * lane, N - 4), lds + x3_cvec_base(NBLK, LN_ANY, RINGN) + par * X3_CVEC_BYTES + wid * 1024);
+    if (src != nullptr) glds16(src + min(n0c + 4 * lane, N - 4), lds + x3_cvec_base(LN_ANY, RINGN) + par * X3_CVEC_BYTES + wid * 1024);
   };
   {
     int m0f, n0f;
@@ -455,21 +407,20 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
     cvec_dma(n0f, 0);
   }
   p16x8 wh[2], wl[2], wnh[2], wnl[2];
-  // PIPE: the W stream lives in four half-step slots (slot 2 * (step parity) + k sub-step; hi and lo plane fragment each),
-  // refilled IN PLACE for two steps later as soon as their last MFMA has been issued -- 32 VGPRs, 1.5 steps of cover
-  p16x8 wsh[4 * NCB] = {}, wsl[4 * NCB] = {};   // slot q, column block cb: [q * NCB + cb]  (zero: the first refill formally reads its slot)
+  // PIPE: the W stream lives in four slots (slot 2 * (step parity) + column half; hi and lo plane fragment each), refilled
+  // IN PLACE for two steps later behind the step's last MFMA -- 32 VGPRs, one step of cover
+  p16x8 wsh[4] = {}, wsl[4] = {};   // (zero: the first refill formally reads its slot)
   uint32_t wso = 0;           // element offset of the W stream's current step inside the fragment-ordered planes
   uint32_t wtile = 0;         // ... of its tile's first step (wave-uniform): changes only when the stream enters a new tile
   auto aim_w_tile = [&]() {
     int m0w, n0w;
     tile_origin(wv, m0w, n0w);
-    wtile = (uint32_t)((n0w >> 5) + wid * NCB) * (uint32_t)wk16 * 512u;   // (column block cb: + cb * wk16 * 512)
+    wtile = (uint32_t)((n0w >> 5) + wid) * (uint32_t)wk16 * 512u;
   };
-  // M16: the fragment-ordered planes serve the 16x16x32 B operand of column half c through a per-lane remap -- lane l reads block
-  // k/16 = 2 step + (l >> 5), slot 16 c + (l & 15) + 32 ((l >> 4) & 1): every 16 lanes one contiguous 256 bytes.  load_w_half's
-  // `ks` is then the column half (+128 elements) instead of the k sub-step (+512).
-  const uint32_t lane_wo = M16 ? (uint32_t)((lane >> 5) * 512 + ((lane & 15) + 32 * ((lane >> 4) & 1)) * 8) : (uint32_t)lane * 8u;
-  constexpr uint32_t W_HALF = M16 ? 128u : 512u;
+  // the fragment-ordered planes serve the 16x16x32 B operand of column half c through a per-lane remap -- lane l reads block
+  // k/16 = 2 step + (l >> 5), slot 16 c + (l & 15) + 32 ((l >> 4) & 1): every 16 lanes one contiguous 256 bytes; column half 1 lies
+  // 128 elements behind half 0
+  const uint32_t lane_wo = (uint32_t)((lane >> 5) * 512 + ((lane & 15) + 32 * ((lane >> 4) & 1)) * 8);
   auto aim_w = [&]() { wso = wtile + (uint32_t)wkk * 1024u + lane_wo; };
   auto advance_w = [&]() {
     if (++wkk == nk) {
@@ -477,36 +428,16 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
       if (wv + gstride < total) { wv += gstride; aim_w_tile(); }
     }
   };
-  auto load_w_half = [&](int ks, auto q_tag) __attribute__((always_inline)) {   // in-place refill of slot q (common.h gload16_refill)
+  auto load_w_half = [&](int c, auto q_tag) __attribute__((always_inline)) {   // in-place refill of slot q (common.h gload16_refill)
     constexpr int q = decltype(q_tag)::value;
-#pragma unroll
-    for (int cb = 0; cb < NCB; ++cb) {
-      const uint32_t o = wso + (uint32_t)cb * (uint32_t)wk16 * 512u + W_HALF * (uint32_t)ks;
-#ifdef MDM_X3_PIPE_NOGUARD
-      gload16_async(wsh[q * NCB + cb], W.hi + o);
-      gload16_async(wsl[q * NCB + cb], W.lo + o);
-#else
-      gload16_refill(wsh[q * NCB + cb], W.hi + o);
-      gload16_refill(wsl[q * NCB + cb], W.lo + o);
-#endif
-    }
-  };
-  // counted wait naming slot q's registers (all column blocks); closing wait over every slot
-  auto wait_slot = [&](auto n_tag, auto q_tag) __attribute__((always_inline)) {
-    constexpr int n = decltype(n_tag)::value, q = decltype(q_tag)::value;
-    if constexpr (NCB == 1) vmem_wait<n>(wsh[q], wsl[q]);
-    else vmem_wait<n>(wsh[2 * q], wsl[2 * q], wsh[2 * q + 1], wsl[2 * q + 1]);
+    const uint32_t o = wso + 128u * (uint32_t)c;
+    gload16_refill(wsh[q], W.hi + o);
+    gload16_refill(wsl[q], W.lo + o);
   };
   auto wait_all_slots = [&]() __attribute__((always_inline)) {
-    static_for<NCB>([&](auto c_tag) __attribute__((always_inline)) {
-      constexpr int c4 = 4 * decltype(c_tag)::value;
-      vmem_wait<0>(wsh[c4], wsl[c4], wsh[c4 + 1], wsl[c4 + 1], wsh[c4 + 2], wsl[c4 + 2], wsh[c4 + 3], wsl[c4 + 3]);
-    });
+    vmem_wait<0>(wsh[0], wsl[0], wsh[1], wsl[1], wsh[2], wsl[2], wsh[3], wsl[3]);
   };
   int gs = 0;                 // PIPE: global k-step counter of this workgroup (stage of step g = g & 3)
-#if defined(MDM_X3_PIPE_PRIO) && !defined(MDM_EMU)
-  if constexpr (PIPE) { if (wid >= 4) __builtin_amdgcn_s_setprio(1); }   // (A/B build: static priority for the younger half)
-#endif
   if constexpr (PIPE) {
     // A(0), A(1), A(2) into stages 0..2 and W(0), W(1) into the four slots; everything landed and visible before step 0
 #pragma unroll
@@ -539,32 +470,27 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
   for (; v < total; v += gstride, tile_parity ^= 1) {
     int m0, n0;
     tile_origin(v, m0, n0);
-    f32x16 accs_[NCB][NT32];     // [column block of the wave][row sub-tile]
-    f32x4 acc16s_[NCB][2];       // T16: rows 192-207 x columns 0-15 / 16-31 of each column block
-    constexpr int NS16 = 2 * X3_MSUB - 1;                   // M16: 13 row slices of 16
-    f32x4 accm_[M16 ? NS16 : 1][2];                         // M16: [row slice][column half], 104 VGPRs like the 32x32 form
-    if constexpr (M16) {
+    f32x16 acc[NT32];            // step-synchronous loop: [row sub-tile]
+    f32x4 acc16[2];              // ... T16: rows 192-207 x columns 0-15 / 16-31
+    constexpr int NS16 = 2 * X3_MSUB - 1;                   // PIPE: 13 row slices of 16
+    f32x4 accm_[PIPE ? NS16 : 1][2];                        // PIPE: [row slice][column half], 104 VGPRs
+    if constexpr (PIPE) {
 #pragma unroll
       for (int s = 0; s < NS16; ++s) accm_[s][0] = accm_[s][1] = f32x4{0.f, 0.f, 0.f, 0.f};
     } else {
 #pragma unroll
-      for (int cb = 0; cb < NCB; ++cb) {
+      for (int t = 0; t < NT32; ++t)
 #pragma unroll
-        for (int t = 0; t < NT32; ++t)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) accs_[cb][t][e] = 0.f;
-        acc16s_[cb][0] = f32x4{0.f, 0.f, 0.f, 0.f};
-        acc16s_[cb][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
+        for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+      acc16[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+      acc16[1] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    f32x16 (&acc)[NT32] = accs_[0];       // the one-block forms (step-synchronous loop) work on block 0
-    f32x4 (&acc16)[2] = acc16s_[0];
-    const int ncol0_w = n0 + wid * NCB * 32;             // this wave's first column (wave-uniform)
+    const int ncol0 = n0 + wid * 32;                     // this wave's first column (wave-uniform)
     // this tile's per-column epilogue vectors are in LDS buffer `tile_parity` (requested one tile ago / in the prologue: no
     // global-load latency in front of the epilogue); the next tile's are requested in this tile's SECOND k step (below),
     // i.e. behind a workgroup barrier every wave reaches only after its epilogue of the previous tile -- whose vectors
     // live in the buffer being refilled -- and land under the rest of this tile's k-loop
-    const float* const cvec = reinterpret_cast<const float*>(lds + x3_cvec_base(NBLK, LN_ANY, RINGN) + tile_parity * X3_CVEC_BYTES);
+    const float* const cvec = reinterpret_cast<const float*>(lds + x3_cvec_base(LN_ANY, RINGN) + tile_parity * X3_CVEC_BYTES);
     const int kt_cvec = nk > 1 ? 1 : 0;
     if (nk == 1) wg_barrier();   // single-step contractions: no k-step barrier in front of the request
     // row statistics (mean, rstd) of this tile's rows, built HERE -- where the accumulators are not live yet -- from the
@@ -572,7 +498,7 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
     // next tile's partials are requested now and land under this tile's k-loop.  Tables and raw buffers alternate with
     // the tile parity: a fast wave may build table j+1 while a slow one still reads table j in its epilogue.
     constexpr bool LN_TABS = FOLD || RES == 3;
-    float2* const stab = reinterpret_cast<float2*>(lds + x3_tab_base(NBLK, RINGN) + tile_parity * X3_TAB_BYTES);
+    float2* const stab = reinterpret_cast<float2*>(lds + x3_tab_base(RINGN) + tile_parity * X3_TAB_BYTES);
     if constexpr (LN_TABS) {
       if (tid < X3_TM) {
         // rows of the tile past the matrix (the last sequence's pad rows) have no statistics: their raw slots hold whatever the
@@ -582,7 +508,7 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
         int m0t, n0t;
         tile_origin(v, m0t, n0t);
         const bool pad_row = m0t + tid >= M;
-        const float* sraw = reinterpret_cast<const float*>(lds + x3_raw_base(NBLK, RINGN) + tile_parity * X3_RAW_BYTES);
+        const float* sraw = reinterpret_cast<const float*>(lds + x3_raw_base(RINGN) + tile_parity * X3_RAW_BYTES);
         // partials are (sum, CENTRED sum of squares about the partial's own mean) of X3_TN columns each; merged by Chan's
         // formula -- no E[x^2] - mean^2 cancellation when a row's mean is large against its spread
         float s1 = 0.f;
@@ -612,17 +538,23 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
     }
     float2* const atab = stab;   // FOLD: statistics of the A rows;  RES == 3: of the residual rows (a kernel has one)
     float2* const rtab = stab;
-#ifdef MDM_X3_DBG
-    unsigned long long dbg_t0 = 0, dbg_w0 = 0, dbg_w1 = 0, dbg_bar = 0;
-    if constexpr ((ABL & 128) != 0) dbg_t0 = x3_now();
-#endif
-    if constexpr (M16) {
-      // ================= pipelined k-loop on v_mfma_f32_16x16x32_f16 (round 7) =================
-      // The streams, stages, waits and the rendezvous of the 32x32x16 form below; the matrix work is 13 elements per 32-deep step,
-      // one per 16-row slice s: two ds_read_b128 (Ah, Al of rows 16 s + (lane & 15), k chunk lane >> 4 -- the T16 read pattern,
-      // conflict-free under x3_swz; 2-way under the plain (row >> 2) & 3 of rounds 1-7) and six MFMAs, the three products of each column half interleaved (acc[s][0], acc[s][1], ...: the two
-      // chains hide each other's dependency).  Under the power limit the 16x16x32 shape delivers more FLOP/s than 32x32x16 at the
-      // same cycles per FLOP (MI355X_MICROARCH.md, "DVFS give-back").
+    if constexpr (PIPE) {
+      // ================= pipelined k-loop on v_mfma_f32_16x16x32_f16 =================
+      // What the step-synchronous loop below pays per 32-deep step -- a full vmcnt(0) drain of loads issued at most one step
+      // earlier, a rendezvous of all eight waves behind it, and a cold restart of the fragment-read pipeline (measured: a
+      // step takes ~2.8 us against 1.3 us of matrix work) -- is removed by running every stream AHEAD of the matrix work:
+      //   * A: four LDS stages.  During step g the pieces of A(g+3) are issued (into the stage A(g-1) lived in); each wave
+      //     retires its own pieces of A(g+1) with a COUNTED vmcnt at the step's middle, then one bare s_barrier -- no drain --
+      //     makes them visible, and from there on the fragment reads of step g+1 may begin: the element pipeline never restarts
+      //     inside a tile;
+      //   * W: four register slots refilled in place by untracked loads retired with counted waits that name the slot (hipcc
+      //     would drain the LDS-DMA queue for a tracked load).
+      // Other operations that land in the vector-memory queue (column vectors, row statistics, the previous tile's stores) only
+      // make the counted waits (X3M_WAIT_*) stricter: the queue retires in order.
+      // The matrix work is 13 elements per 32-deep step, one per 16-row slice s: two ds_read_b128 (Ah, Al of rows 16 s + (lane & 15),
+      // k chunk lane >> 4 -- the T16 read pattern, conflict-free under x3_swz) and six MFMAs, the three products of each column half
+      // interleaved (acc[s][0], acc[s][1], ...: the two chains hide each other's dependency).  Under the power limit the 16x16x32
+      // shape delivers more FLOP/s than 32x32x16 at the same cycles per FLOP (MI355X_MICROARCH.md, "DVFS give-back").
       //   * both W column halves of step g are read by every element, so slots W0 / W1 of the step are refilled together for
       //     g + 2 behind its last MFMA (cover: one step);
       //   * fragment ring: element e uses slot e % 3, the last element slot 3 -- 13 is not a multiple of 3, and the reads of the
@@ -656,20 +588,14 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
           else issue_reads(std::integral_constant<int, e + DEPTH - NE>{}, nxt);
           // ---- 2. the middle of the step: own pieces of A(g+1) landed, then the rendezvous makes them visible
           if constexpr (e == XB) {
-            vmem_wait<X3M_WAIT_MID + X3P_MID_SLACK>(wsh[W0], wsl[W0], wsh[W1], wsl[W1]);
-#ifndef MDM_EMU
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            vmem_wait<X3M_WAIT_MID>(wsh[W0], wsl[W0], wsh[W1], wsl[W1]);
+            sched_fence();
             wg_barrier_nodrain();   // A(g+1) visible to every wave; every wave is past step g-1, whose stage A(g+3) refills
-#ifndef MDM_EMU
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            sched_fence();
           }
           // ---- 3. this element's reads retired (those of the DEPTH younger elements stay in flight)
           lds_wait<2 * DEPTH>(ah[slot(e)], al[slot(e)]);
-#ifndef MDM_EMU
-          __builtin_amdgcn_sched_barrier(0);  // the MFMAs below must not be hoisted above the wait (rule 18)
-#endif
+          sched_fence();  // the MFMAs below must not be hoisted above the wait (rule 18)
           // ---- 4. matrix work: per column half al*wh, ah*wl, ah*wh (the product order of every form)
 #pragma unroll
           for (int c = 0; c < 2; ++c) accm_[e][c] = mfma16_p16(al[slot(e)], wsh[W0 + c], accm_[e][c]);
@@ -677,14 +603,10 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
           for (int c = 0; c < 2; ++c) accm_[e][c] = mfma16_p16(ah[slot(e)], wsl[W0 + c], accm_[e][c]);
 #pragma unroll
           for (int c = 0; c < 2; ++c) accm_[e][c] = mfma16_p16(ah[slot(e)], wsh[W0 + c], accm_[e][c]);
-#ifndef MDM_EMU
-          __builtin_amdgcn_sched_barrier(0);
-#endif
+          sched_fence();
           // ---- 5. one LDS-DMA piece of A(g+3) rides behind each of the elements that follow the barrier
           if constexpr (e >= XB && e < XB + X3_A_PIECES) piece_a(ca, e - XB, (int)fill);
-#ifndef MDM_EMU
-          __builtin_amdgcn_sched_barrier(0);
-#endif
+          sched_fence();
         });
         // both W slots of the step are free: refill in place for g+2; then both streams move on
         aim_w();
@@ -698,195 +620,6 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
       static_for<DEPTH>([&](auto d_tag) __attribute__((always_inline)) { issue_reads(d_tag, (uint32_t)gs & 3u); });
       for (int kt = 0; kt < nk; kt += 2) {
         pipe_step(std::integral_constant<int, 0>{});
-        if (kt == 0 && v + gstride < total) {   // the next tile's per-column vectors (see the 32x32x16 form)
-          int m0n, n0n;
-          tile_origin(v + gstride, m0n, n0n);
-          cvec_dma(n0n, tile_parity ^ 1);
-        }
-        pipe_step(std::integral_constant<int, 1>{});
-      }
-      // the last step's reads of the next tile's elements 0, 1: retired and dropped (re-primed behind the epilogue)
-      lds_wait<0>(ah[0], al[0], ah[1], al[1]);
-      wait_all_slots();
-    } else if constexpr (PIPE) {
-      // ================= pipelined k-loop (round 3) =================
-      // What the step-synchronous loop below pays per 32-deep step -- a full vmcnt(0) drain of loads issued at most one step
-      // earlier, a rendezvous of all eight waves behind it, and a cold restart of the fragment-read pipeline (measured: a
-      // step takes ~2.8 us against 1.3 us of matrix work) -- is removed by running every stream AHEAD of the matrix work:
-      //   * A: four LDS stages.  During step g the pieces of A(g+3) are issued (into the stage A(g-1) lived in); each wave
-      //     retires its own pieces of A(g+1) with a COUNTED vmcnt at the step's middle, then one bare s_barrier -- no drain --
-      //     makes them visible, and from there on the fragment reads of step g+1 may begin: the unit pipeline never restarts
-      //     inside a tile.  cover: 1.5-2 steps.
-      //   * W: four half-step register slots refilled in place for step g+2 right behind their last MFMA (cover 1.5 steps),
-      //     by untracked loads retired with counted waits that name the slot (hipcc would drain the LDS-DMA queue for a
-      //     tracked load).
-      //   * the 16-row sub-tile ("X") sits between the two k sub-steps, right behind the barrier, where both W halves of the
-      //     step are valid; its two reads travel in the same in-order read queue as the units'.
-      // Per step and wave the vector-memory queue therefore holds, in program order,
-      //     W0(g+2) x2 | A(g+3) x nA | W1(g+2) x2          nA = 4 (waves 0, 1) or 3
-      // and the waits are: step start, slot W0(g): 2 nA + 6 younger operations; middle, A(g+1) and W1(g): nA + 4.
-      // Other operations that land in the queue (column vectors, row statistics, the previous tile's stores) only make
-      // these waits stricter: the queue retires in order.
-#ifndef MDM_X3_PIPE_DEPTH
-#define MDM_X3_PIPE_DEPTH 2
-#endif
-      constexpr int NU = 2 * NT32, NE = NU + 1, XP = NT32, DEPTH = MDM_X3_PIPE_DEPTH, RING = DEPTH + 1;
-      // counted waits, generalised: a half-step slot is LWH = 2 NCB loads, a wave issues at least NA_MIN = 26 / WAVES pieces per step
-      //   step start, slot W0(g): younger = A(g+1) + W1(g) + W0(g+1) + A(g+2) + W1(g+1) = 2 NA_MIN + 3 LWH   (8 waves: 12)
-      //   middle, A(g+1) and W1(g): younger = W0(g+1) + A(g+2) + W1(g+1) = NA_MIN + 2 LWH                  (8 waves: 7)
-      constexpr int LWH = 2 * NCB, NA_MIN = 26 / X3_WAVES;
-      constexpr int WAIT_WS = (NCB == 1 && X3_WAVES == 8) ? X3P_WAIT_WS : 2 * NA_MIN + 3 * LWH;
-      constexpr int WAIT_MID = (NCB == 1 && X3_WAVES == 8) ? X3P_WAIT_MID : NA_MIN + 2 * LWH;
-      static_assert((NCB == 1 && X3_WAVES == 8) || (WAIT_WS == 24 && WAIT_MID == 14), "wide form: 4 waves x 2 column blocks");
-      static_assert(NU % RING == 0, "fragment ring slots must line up across steps");
-      p16x8 ah[RING], al[RING], a16h, a16l;
-#ifndef MDM_EMU
-      const uint32_t lane_a = lds_base + fa, lane_a16 = lds_base + fa16;
-      const uint32_t sw0 = (uint32_t)((h ^ sw) * 16), sw1 = (uint32_t)(((2 + h) ^ sw) * 16);
-#endif
-      // reads of element `ee` of the step whose A stage is `stg` (runtime, 0..3): a regular unit or the 16-row sub-tile
-      auto issue_reads = [&](auto ee_tag, uint32_t stg) __attribute__((always_inline)) {
-        constexpr int ee = decltype(ee_tag)::value;
-        if constexpr (ee == XP) {
-#ifdef MDM_EMU
-          lds_read16(a16h, lds + stg * X3_A_STAGE, fa16);
-          lds_read16(a16l, lds + stg * X3_A_STAGE, X3_A_BYTES + fa16);
-#else
-          lds_read16<0>(a16h, lane_a16 + stg * X3_A_STAGE);
-          lds_read16<X3_A_BYTES>(a16l, lane_a16 + stg * X3_A_STAGE);
-#endif
-        } else {
-          constexpr int u = ee < XP ? ee : ee - 1, ks = u / NT32, t = u - ks * NT32;
-#ifdef MDM_EMU
-          lds_read16(ah[u % RING], lds + stg * X3_A_STAGE, fa + t * 2048 + (((ks * 2 + h) ^ sw) * 16));
-          lds_read16(al[u % RING], lds + stg * X3_A_STAGE, X3_A_BYTES + fa + t * 2048 + (((ks * 2 + h) ^ sw) * 16));
-#else
-          const uint32_t ad = lane_a + stg * X3_A_STAGE + (ks ? sw1 : sw0);
-          lds_read16<t * 2048>(ah[u % RING], ad);
-          lds_read16<X3_A_BYTES + t * 2048>(al[u % RING], ad);
-#endif
-        }
-      };
-      auto pipe_step = [&](auto par_tag) __attribute__((always_inline)) {
-        constexpr int PAR = decltype(par_tag)::value;
-        const uint32_t cur = (uint32_t)gs & 3u, nxt = (uint32_t)(gs + 1) & 3u, fill = (uint32_t)(gs + 3) & 3u;
-        p16x8 w16h[NCB][2], w16l[NCB][2];
-#ifdef MDM_X3_PIPE_NOLOOK
-        static_for<DEPTH>([&](auto d_tag) __attribute__((always_inline)) { issue_reads(d_tag, cur); });
-#endif
-        // slot W0(g) landed?  (issued in the middle of step g-2)
-        wait_slot(std::integral_constant<int, WAIT_WS>{}, std::integral_constant<int, 2 * PAR>{});
-        static_for<NE>([&](auto e_tag) __attribute__((always_inline)) {
-          constexpr int e = decltype(e_tag)::value;
-          // ---- 1. reads of the element DEPTH ahead (past the step: units 0, 1 of step g+1, from the next stage)
-          if constexpr (e + DEPTH < NE) issue_reads(std::integral_constant<int, e + DEPTH>{}, cur);
-#ifndef MDM_X3_PIPE_NOLOOK   // (bisection build: the fragment pipeline restarts at every step)
-          else issue_reads(std::integral_constant<int, e + DEPTH - NE>{}, nxt);
-#endif
-          // ---- 2. the middle of the step sits in front of the 16-row sub-tile
-          if constexpr (e == XP) {
-            // own pieces of A(g+1) and slot W1(g) (both issued during step g-2) landed
-            wait_slot(std::integral_constant<int, WAIT_MID + X3P_MID_SLACK>{}, std::integral_constant<int, 2 * PAR + 1>{});
-#if (defined(MDM_X3_PIPE_SNOP) || defined(MDM_X3_PIPE_SNOP2)) && !defined(MDM_EMU)   // (bisection build: the matrix pipe drains before slot W0 is rewritten)
-            asm volatile("s_nop 15\n s_nop 15\n s_nop 15\n s_nop 15\n s_nop 15\n s_nop 15\n s_nop 15\n s_nop 15" ::: "memory");
-#endif
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) {
-              w16h[cb][0] = wsh[(2 * PAR) * NCB + cb]; w16h[cb][1] = wsh[(2 * PAR + 1) * NCB + cb];
-              w16l[cb][0] = wsl[(2 * PAR) * NCB + cb]; w16l[cb][1] = wsl[(2 * PAR + 1) * NCB + cb];
-              frag32_to_frag16(w16h[cb][0], w16h[cb][1]);
-              frag32_to_frag16(w16l[cb][0], w16l[cb][1]);
-            }
-#ifndef MDM_EMU
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-            // slot W0 is free (its last 32-row MFMA was issued with unit NT32-1, its lane-swapped copy is taken): refill for g+2
-            if constexpr (!(ABL & 2)) { aim_w(); load_w_half(0, std::integral_constant<int, 2 * PAR>{}); }
-#ifdef MDM_X3_PIPE_DRAINBAR   // (bisection build: lgkmcnt(0) in front of the rendezvous)
-            lds_wait<0>(a16h, a16l);
-            wg_barrier();
-#else
-            wg_barrier_nodrain();   // A(g+1) visible to every wave; every wave is past step g-1, whose stage A(g+3) refills
-#endif
-#ifndef MDM_EMU
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-          }
-          // ---- 3. this element's reads retired (those of the DEPTH younger elements may stay in flight)
-#ifdef MDM_X3_PIPE_NOLOOK
-          constexpr int issued_after = (NE - 1 - e) < DEPTH ? (NE - 1 - e) : DEPTH;
-#else
-          constexpr int issued_after = DEPTH;
-#endif
-          if constexpr (e == XP) {
-            lds_wait<2 * issued_after>(a16h, a16l);
-          } else {
-            constexpr int u = e < XP ? e : e - 1;
-            lds_wait<2 * issued_after>(ah[u % RING], al[u % RING]);
-          }
-#ifndef MDM_EMU
-          __builtin_amdgcn_sched_barrier(0);  // the MFMAs below must not be hoisted above the wait (rule 18)
-#endif
-          // ---- 4. matrix work
-          if constexpr (e == XP) {
-            if constexpr ((ABL & 4) != 0) {
-#ifndef MDM_EMU
-              asm volatile("" ::"v"(a16h), "v"(a16l), "v"(w16h[0][0]), "v"(w16h[0][1]), "v"(w16l[0][0]), "v"(w16l[0][1]));
-#endif
-            } else {
-#pragma unroll
-              for (int wb = 0; wb < NCB; ++wb)
-#pragma unroll
-                for (int cb = 0; cb < 2; ++cb) {
-                  acc16s_[wb][cb] = mfma16_p16(a16l, w16h[wb][cb], acc16s_[wb][cb]);
-                  acc16s_[wb][cb] = mfma16_p16(a16h, w16l[wb][cb], acc16s_[wb][cb]);
-                  acc16s_[wb][cb] = mfma16_p16(a16h, w16h[wb][cb], acc16s_[wb][cb]);
-                }
-            }
-          } else {
-            constexpr int u = e < XP ? e : e - 1, ks = u / NT32, t = u - ks * NT32;
-            if constexpr ((ABL & 4) != 0) {
-#ifndef MDM_EMU
-              asm volatile("" ::"v"(al[u % RING]), "v"(ah[u % RING]), "v"(wsh[(2 * PAR + ks) * NCB]), "v"(wsl[(2 * PAR + ks) * NCB]));
-#endif
-            } else {
-              // (the wave's column blocks interleaved: consecutive MFMAs on different accumulators, one A fragment pair for all)
-#pragma unroll
-              for (int wb = 0; wb < NCB; ++wb) accs_[wb][t] = mfma_p16(al[u % RING], wsh[(2 * PAR + ks) * NCB + wb], accs_[wb][t]);
-#pragma unroll
-              for (int wb = 0; wb < NCB; ++wb) accs_[wb][t] = mfma_p16(ah[u % RING], wsl[(2 * PAR + ks) * NCB + wb], accs_[wb][t]);
-#pragma unroll
-              for (int wb = 0; wb < NCB; ++wb) accs_[wb][t] = mfma_p16(ah[u % RING], wsh[(2 * PAR + ks) * NCB + wb], accs_[wb][t]);
-            }
-          }
-#ifndef MDM_EMU
-          __builtin_amdgcn_sched_barrier(0);  // keep the same-accumulator triple back to back (no filler inside)
-#endif
-          // ---- 5. one LDS-DMA piece of A(g+3) rides behind each of the four elements that follow the barrier
-          if constexpr (!(ABL & 2) && e >= XP && e < XP + X3_A_PIECES) piece_a(ca, e - XP, (int)fill);
-#ifndef MDM_EMU
-          __builtin_amdgcn_sched_barrier(0);
-#endif
-        });
-        // slot W1 is free: refill for g+2; then both streams move on
-#if defined(MDM_X3_PIPE_SNOP2) && !defined(MDM_EMU)   // (bisection build: the matrix pipe drains before slot W1 is rewritten)
-        asm volatile("s_nop 15\n s_nop 15\n s_nop 15\n s_nop 15\n s_nop 15\n s_nop 15\n s_nop 15\n s_nop 15" ::: "memory");
-#endif
-        if constexpr (!(ABL & 2)) load_w_half(1, std::integral_constant<int, 2 * PAR + 1>{});
-        advance_w();
-        advance_a(ca);
-        ++gs;
-      };
-#ifdef MDM_X3_PIPE_SYNCTILE   // (bisection build: every tile starts from a drained, rendezvoused workgroup)
-      wait_vmem_all();
-      wg_barrier();
-#endif
-      // prime the fragment pipeline of this tile: its first stage was made visible by the previous step's barrier / the prologue
-#ifndef MDM_X3_PIPE_NOLOOK
-      static_for<DEPTH>([&](auto d_tag) __attribute__((always_inline)) { issue_reads(d_tag, (uint32_t)gs & 3u); });
-#endif
-      for (int kt = 0; kt < nk; kt += 2) {
-        pipe_step(std::integral_constant<int, 0>{});
         // the next tile's per-column vectors: behind step 0's barrier, which every wave reaches only after its epilogue of
         // the previous tile (whose vectors live in the buffer being refilled)
         if (kt == 0 && v + gstride < total) {
@@ -896,17 +629,14 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
         }
         pipe_step(std::integral_constant<int, 1>{});
       }
-      // the tile's last step has run two elements ahead like every other (ONE step body: a separate "last step" instance made
-      // hipcc keep two copies of the accumulators, 192 VGPRs): those fragments belong to the next tile's first step, whose
-      // pipeline is primed afresh behind the epilogue -- retire and drop them
-#ifndef MDM_X3_PIPE_NOLOOK
-      if constexpr (DEPTH == 2) lds_wait<0>(ah[0], al[0], ah[1], al[1]);
-      else lds_wait<0>(ah[0], al[0], ah[1], al[1], ah[2], al[2]);
-#endif
+      // the tile's last step has run two elements ahead like every other (ONE step body): those fragments belong to the next
+      // tile's first step, whose pipeline is primed afresh behind the epilogue -- retire and drop them
+      lds_wait<0>(ah[0], al[0], ah[1], al[1]);
       // the epilogue must not meet a W slot whose load is still in flight (a spill would save the stale register); hipcc
       // drains the queue in front of the epilogue's first LDS read anyway (LDS-DMA pending)
       wait_all_slots();
     } else {
+    // ================= step-synchronous k-loop on v_mfma_f32_32x32x16_f16 =================
     for (int kt = 0; kt < nk; ++kt) {
       if (kt == kt_cvec && v + gstride < total) {
         int m0n, n0n;
@@ -918,10 +648,10 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
         wkk = 0;
         if (wv + gstride < total) wv += gstride;
       }
-      if (!(ABL & 2)) load_w(wv, wkk, wnh, wnl);
+      load_w(wv, wkk, wnh, wnl);
       // 14 units per stage (2 k sub-steps x 7 row sub-tiles), each = 2 A-fragment reads + 3 MFMAs, software-pipelined
       // DEPTH units deep: the reads of unit u+DEPTH are issued, then a COUNTED wait (2*DEPTH younger reads may stay in
-      // flight) retires unit u's, then its 3 MFMAs go.  One LDS-DMA piece of A(g+1) rides behind each of the first seven.
+      // flight) retires unit u's, then its 3 MFMAs go.  One LDS-DMA piece of A(g+1) rides behind each of the first four.
       constexpr int DEPTH = 2, RING = DEPTH + 1;  // fragment-read lookahead in units
       p16x8 ah[RING], al[RING];
 #ifdef MDM_EMU
@@ -954,7 +684,7 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
       p16x8 f6_hold = {0, 0, 0, 0, 0, 0, 0, 0};   // F6 only
       static_for<NU + DEPTH>([&](auto u_tag) __attribute__((always_inline)) {
         constexpr int u = decltype(u_tag)::value;
-        if constexpr (u < NU && (!(ABL & 64) || u % 2 == 0)) {   // 64: timing experiment -- half the fragment reads
+        if constexpr (u < NU) {
           constexpr int ks = F6 ? (u & 1) : u / NT32, t = F6 ? (u >> 1) : u - ks * NT32;
           X3_RD_A(ah[u % RING], 0, t, ks);
           X3_RD_A(al[u % RING], 1, t, ks);
@@ -965,16 +695,8 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
           constexpr int younger = 2 * ((NU - 1 - uv) < DEPTH ? (NU - 1 - uv) : DEPTH);
           if constexpr (T16 && uv == 0) lds_wait<younger>(ah[uv % RING], al[uv % RING], a16h, a16l);
           else lds_wait<younger>(ah[uv % RING], al[uv % RING]);
-#ifndef MDM_EMU
-          __builtin_amdgcn_sched_barrier(0);  // the MFMAs below must not be hoisted above the wait (rule 18)
-#endif
-          if constexpr ((ABL & 4) != 0 || ((ABL & 32) != 0 && uv == NU - 1)) {
-            // 4: no MFMAs at all; 32: timing experiment -- one unit of 14 skipped = the MFMA work a 16-row last sub-tile
-            // (208 instead of 224 rows per tile) would save
-#ifndef MDM_EMU
-            asm volatile("" ::"v"(al[uv % RING]), "v"(ah[uv % RING]), "v"(wh[ks]), "v"(wl[ks]));
-#endif
-          } else if constexpr (F6) {
+          sched_fence();  // the MFMAs below must not be hoisted above the wait (rule 18)
+          if constexpr (F6) {
             // main term on fp16; the record's first 16 bytes (code dwords c0-c3) wait in f6_hold for the second read
             // (c4, c5, scale) of the same sub-tile, then ONE scaled MFMA adds both cross terms of the 32-k block
             if constexpr (ks == 0) {
@@ -988,22 +710,6 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
               const i32x8 w6 = {(int)w0[0], (int)w0[1], (int)w0[2], (int)w0[3], (int)w1[0], (int)w1[1], 0, 0};
               acc[t] = mfma_mx_fp6(a6, w6, acc[t], (int)c1[2], (int)w1[2]);
             }
-          } else if constexpr ((ABL & 256) != 0) {
-            // 256: timing experiment -- the INSTRUCTION MIX of the f16f6 scheme (gemm_f16f6.h) inside this kernel's skeleton:
-            // per row sub-tile and 32 k, two main-term MFMAs (fp16 and bf16 run at the same rate) and ONE scaled MX-FP6 MFMA
-            // (both cross terms of 32 k fill its K = 64); loads, LDS traffic and barriers as in production (the planned plane
-            // records have the bytes of today's lo plane).  Operands of the scaled MFMA are whatever bits the lo fragments
-            // hold: results are garbage, only the time is representative.
-            acc[t] = mfma_p16(ah[uv % RING], wh[ks], acc[t]);
-#ifndef MDM_EMU
-            if constexpr (ks == 0) {
-              const u32x4 qa0 = __builtin_bit_cast(u32x4, al[uv % RING]), qa1 = __builtin_bit_cast(u32x4, ah[uv % RING]);
-              const u32x4 qb0 = __builtin_bit_cast(u32x4, wl[0]), qb1 = __builtin_bit_cast(u32x4, wl[1]);
-              const i32x8 qa = {(int)qa0[0], (int)qa0[1], (int)qa0[2], (int)qa0[3], (int)qa1[0], (int)qa1[1], 0, 0};
-              const i32x8 qb = {(int)qb0[0], (int)qb0[1], (int)qb0[2], (int)qb0[3], (int)qb1[0], (int)qb1[1], 0, 0};
-              acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(qa, qb, acc[t], 2, 2, 0, 120 + (lane & 7), 0, 121 + (lane & 3));
-            }
-#endif
           } else {
             acc[t] = mfma_p16(al[uv % RING], wh[ks], acc[t]);
             acc[t] = mfma_p16(ah[uv % RING], wl[ks], acc[t]);
@@ -1017,38 +723,17 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
               }
             }
           }
-#ifndef MDM_EMU
-          __builtin_amdgcn_sched_barrier(0);  // keep the same-accumulator triple back to back (no filler inside)
-#endif
-          if constexpr (!(ABL & 2) && uv < X3_A_PIECES) piece_a(ca, uv, abuf ^ 1);
-#ifndef MDM_EMU
-          __builtin_amdgcn_sched_barrier(0);
-#endif
+          sched_fence();  // keep the same-accumulator triple back to back (no filler inside)
+          if constexpr (uv < X3_A_PIECES) piece_a(ca, uv, abuf ^ 1);
+          sched_fence();
         }
       });
 #undef X3_RD_A
       advance_a(ca);
-#ifdef MDM_X3_DBG
-      if constexpr ((ABL & 128) != 0) {
-        const unsigned long long a0 = x3_now();
-        wait_vmem_all();
-        const unsigned long long a1 = x3_now();
-        if (kt == 0) dbg_w0 += a1 - a0; else dbg_w1 += a1 - a0;
-      }
-#endif
-      if (!(ABL & 8)) wait_vmem_all();   // 8: experiment -- loads issued but never waited for (results are garbage)
-#ifdef MDM_X3_DBG
-      if constexpr ((ABL & 128) != 0) {
-        const unsigned long long b0 = x3_now();
-        wg_barrier();
-        dbg_bar += x3_now() - b0;
-      }
-#endif
+      wait_vmem_all();
       wg_barrier();
       abuf ^= 1;
-      if (!(ABL & 2)) {
-        wh[0] = wnh[0]; wh[1] = wnh[1]; wl[0] = wnl[0]; wl[1] = wnl[1];
-      }
+      wh[0] = wnh[0]; wh[1] = wnh[1]; wl[0] = wnl[0]; wl[1] = wnl[1];
     }
     }   // !PIPE
 
@@ -1057,19 +742,12 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
     // each wave transposes 8 rows x 32 columns at a time (accumulator registers 4g..4g+3 of both lane halves) through
     // its private 1 KB LDS patch -- disjoint from the A stages, which already hold the next tile's first stage
     // -- and writes 16 bytes per lane: lane -> (row = lane>>3, 4 consecutive columns).
-#ifdef MDM_X3_DBG
-    unsigned long long dbg_t1 = 0;
-    if constexpr ((ABL & 128) != 0) dbg_t1 = x3_now();
-#endif
-    static_for<NCB>([&](auto cbk_tag) __attribute__((always_inline)) {   // the wave's column blocks, one after the other
-    constexpr int cbk = decltype(cbk_tag)::value;
-    f32x16 (&acc)[NT32] = accs_[cbk];
-    f32x4 (&acc16)[2] = acc16s_[cbk];
-    const int wblk = wid * NCB + cbk;               // this pass's 32-column block inside the tile (wave-uniform)
-    const int ncol0 = ncol0_w + cbk * 32;           // ... and its first column
-    {   // epilogue scope: every lane-derived index below is rebuilt from an OPAQUE copy of the lane id, so that hipcc cannot
+    [&]() __attribute__((always_inline)) {
+        // epilogue scope: every lane-derived index below is rebuilt from an OPAQUE copy of the lane id, so that hipcc cannot
         // compute the epilogue's per-round offsets once, in front of the tile loop, and carry them (24 VGPRs of hoisted
-        // store offsets, spilled in the in_proj instantiation) through every k-loop
+        // store offsets, spilled in the in_proj instantiation) through every k-loop.  (A lambda called in place, not a plain
+        // block: hipcc schedules 21 of the 28 instantiations differently for the block, and every measurement of this kernel
+        // was taken on this form.)
     int lane_e = lane;
 #ifndef MDM_EMU
     asm volatile("" : "+v"(lane_e));
@@ -1080,7 +758,7 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
     const int prow = lane_e >> 3, pc4 = (lane_e & 7) * 4;
     const int n4 = ncol0 + pc4;                          // first of this lane's 4 columns in the row layout
     // per-lane column vectors of the row-major side: bias (or folded bias), Q scale, folded column sums, residual gamma/beta
-    const int cl4 = wblk * 32 + pc4;                      // this lane's first column inside the tile
+    const int cl4 = wid * 32 + pc4;                      // this lane's first column inside the tile
     const float4 b4 = ld4(cvec + cl4);
     // column scale (in_proj's Q columns; scale_cols is a multiple of the tile width): only the instantiations without an
     // activation and without a plane residual carry one (the launcher refuses it elsewhere) -- two packed multiplies per round
@@ -1093,9 +771,9 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
       be4 = ld4(cvec + 768 + cl4);
     }
     // the same in the accumulator layout (lane -> column r of the wave's 32): V^T path
-    const float bias = cvec[wblk * 32 + r];
+    const float bias = cvec[wid * 32 + r];
     float csum = 0.f;
-    if constexpr (FOLD) csum = cvec[256 + wblk * 32 + r];
+    if constexpr (FOLD) csum = cvec[256 + wid * 32 + r];
     // accumulator values of one round, row-major, -> the GEMM's value:  fold / bias, activation, Q scale
     const float accs = ep.acc_scale;
     // RES == 3: the rebuilt LayerNorm residual's beta is a per-column constant like the bias -- added with it
@@ -1126,7 +804,7 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
     // the VALU work of the next (a wave's LDS operations execute in order).
     auto patch_write = [&](auto j_tag) __attribute__((always_inline)) {
       constexpr int j = decltype(j_tag)::value, t = j / 4, g = j % 4;
-      if constexpr (M16) {
+      if constexpr (PIPE) {
         // 16x16 accumulators: round j = rows 8 (j % 2) .. + 7 of slice j / 2, held by the lanes with lane >> 5 == j % 2 (as below)
         if constexpr (j < NROUNDS) {
           if (h == j % 2) {
@@ -1164,20 +842,20 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
 #endif
       const int which = ncol_e / Dm, hcol = ncol_e - which * Dm, head = hcol >> 7, d0 = hcol & 127;
       const size_t shq = (size_t)(m0_e / rows_per_tile) * Hq + head;
-      if (ncol0 < N && !(ABL & 1)) {
+      if (ncol0 < N) {
         if (which == 2) {
           // V^T: accumulator registers 8 s2 .. 8 s2 + 7 of a lane ARE positions 8h .. 8h+7 of 16-key group s2
           p16_t* vhp = ep.qkv.vh + ((shq * ep.qkv.NKT) * AX_HD + d0 + r) * 32 + 8 * h;
           p16_t* vlp = ep.qkv.vl + ((shq * ep.qkv.NKT) * AX_HD + d0 + r) * 32 + 8 * h;
           const int nkt = ep.qkv.NKT;
-          if constexpr (M16) {
+          if constexpr (PIPE) {
             // 16x16 accumulators: keys 16 s + 4 (lane >> 4) + e of slice s = key tile s / 2, 16-key group s % 2, positions
             // 4 ((g16 >> 1) + 2 (g16 & 1)) + e of the group (the T16 store below, on every slice); keys 208-223 are never written
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb) {
               const int cl = 16 * cb + r16;                      // this lane's column inside the wave's 32
-              const float b16 = cvec[wblk * 32 + cl];
-              const float c16 = FOLD ? cvec[256 + wblk * 32 + cl] : 0.f;
+              const float b16 = cvec[wid * 32 + cl];
+              const float c16 = FOLD ? cvec[256 + wid * 32 + cl] : 0.f;
               const size_t o0 = (shq * ep.qkv.NKT * AX_HD + d0 + cl) * 32 + 4 * ((g16 >> 1) + 2 * (g16 & 1));
               auto vfin = [&](float a) __attribute__((always_inline)) { return a * accs + b16; };   // (!FOLD: one expression for both uses)
               // PAIR: key 0 of sequence pair_B + b is tile row S -- register S & 3 of slice S >> 4 in the lane of this column whose
@@ -1267,7 +945,7 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
               }
             }
           }
-          }   // !M16
+          }   // !PIPE
         } else {
           // Q / K rows: one base pointer per plane, 32-bit offsets
           p16_t* dh = (which == 0 ? ep.qkv.qh : ep.qkv.kh) + shq * SPq * AX_HD + d0 + pc4;
@@ -1278,33 +956,13 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
           const size_t pq = PAIR ? (size_t)ep.pair_B * Hq * SPq * AX_HD : 0;
           patch_write(std::integral_constant<int, 0>{});
           float2 st_cur = row_stats(std::integral_constant<int, 0>{});
-          float4 v_cur = zero4();
-          if constexpr (X3_EPI_AHEAD) {
-            wave_lds_fence();
-            v_cur = ld4(&patch[prow * 32 + pc4]);
-            wave_lds_fence();
-            patch_write(std::integral_constant<int, 1>{});
-          }
           static_for<NROUNDS>([&](auto j_tag) __attribute__((always_inline)) {
             constexpr int j = decltype(j_tag)::value, t = j / 4, g = j % 4;
-            float4 v4;
-            float2 st_next;
-            if constexpr (X3_EPI_AHEAD) {
-              wave_lds_fence();
-              float4 v_next = zero4();
-              if constexpr (j + 1 < NROUNDS) v_next = ld4(&patch[prow * 32 + pc4]);
-              st_next = row_stats(std::integral_constant<int, j + 1>{});
-              wave_lds_fence();
-              patch_write(std::integral_constant<int, j + 2>{});
-              v4 = v_cur;
-              v_cur = v_next;
-            } else {
-              wave_lds_fence();
-              v4 = ld4(&patch[prow * 32 + pc4]);
-              st_next = row_stats(std::integral_constant<int, j + 1>{});
-              wave_lds_fence();
-              patch_write(std::integral_constant<int, j + 1>{});
-            }
+            wave_lds_fence();
+            float4 v4 = ld4(&patch[prow * 32 + pc4]);
+            const float2 st_next = row_stats(std::integral_constant<int, j + 1>{});
+            wave_lds_fence();
+            patch_write(std::integral_constant<int, j + 1>{});
             const float2 st = st_cur;
             st_cur = st_next;
             if (t < nkt) {
@@ -1386,82 +1044,56 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
                                rl[t % RR][2], rl[t % RR][3]);
         }
       };
-      if (!(ABL & 1)) {
-        res_issue(std::integral_constant<int, 0>{});
-        if constexpr (RR == 3) res_issue(std::integral_constant<int, 1>{});
-      }
-      float2* part = reinterpret_cast<float2*>(lds + x3_part_base(NBLK, RINGN)) + wblk * X3_TM;   // OSTAT: this column block's partials
+      res_issue(std::integral_constant<int, 0>{});
+      if constexpr (RR == 3) res_issue(std::integral_constant<int, 1>{});
+      float2* part = reinterpret_cast<float2*>(lds + x3_part_base(RINGN)) + wid * X3_TM;   // OSTAT: this column block's partials
       patch_write(std::integral_constant<int, 0>{});
       float2 st_cur = row_stats(std::integral_constant<int, 0>{});
-      float4 v_cur = zero4();
-      if constexpr (X3_EPI_AHEAD) {
-        wave_lds_fence();
-        v_cur = ld4(&patch[prow * 32 + pc4]);
-        wave_lds_fence();
-        patch_write(std::integral_constant<int, 1>{});
-      }
       static_for<NROUNDS>([&](auto j_tag) __attribute__((always_inline)) {
         constexpr int j = decltype(j_tag)::value, t = j / 4, g = j % 4;
         if constexpr (HAS_RES && g == 0) {
-          if (!(ABL & 1)) {
-            res_issue(std::integral_constant<int, t + RR - 1>{});
-            res_wait(std::integral_constant<int, t>{});
-          }
+          res_issue(std::integral_constant<int, t + RR - 1>{});
+          res_wait(std::integral_constant<int, t>{});
         }
-        float4 v4;
-        float2 st_next;
-        if constexpr (X3_EPI_AHEAD) {
-          wave_lds_fence();
-          float4 v_next = zero4();
-          if constexpr (j + 1 < NROUNDS) v_next = ld4(&patch[prow * 32 + pc4]);
-          st_next = row_stats(std::integral_constant<int, j + 1>{});
-          wave_lds_fence();
-          patch_write(std::integral_constant<int, j + 2>{});
-          v4 = v_cur;
-          v_cur = v_next;
-        } else {
-          wave_lds_fence();
-          v4 = ld4(&patch[prow * 32 + pc4]);
-          st_next = row_stats(std::integral_constant<int, j + 1>{});
-          wave_lds_fence();
-          patch_write(std::integral_constant<int, j + 1>{});
-        }
+        wave_lds_fence();
+        float4 v4 = ld4(&patch[prow * 32 + pc4]);
+        const float2 st_next = row_stats(std::integral_constant<int, j + 1>{});
+        wave_lds_fence();
+        patch_write(std::integral_constant<int, j + 1>{});
         const float2 st = st_cur;
         st_cur = st_next;
         const int row_in_tile = t * 32 + 8 * g + prow;
         v4 = finish4(v4, st);
-        if (!(ABL & 1)) {
-          if constexpr (RES == 1) {
-            const f32x4 q4 = rr[t % RR][g];
-            v4.x += q4[0]; v4.y += q4[1]; v4.z += q4[2]; v4.w += q4[3];
-          } else if constexpr (RES_PLANES && kSplitF16) {
-            // x = hi + lo (RES == 3: minus the row mean, times rstd * gamma; beta rides in the bias vector bb4): the planes are
-            // converted inside the adds (common.h f16_half_plus), the mean leaves before anything is scaled
-            const u32x2 a = rh[t % RR][g], b = rl[t % RR][g];
-            const float c0 = RES == 3 ? -st.x : 0.f;
-            const float d0 = f16_half_plus<0>(b[0], f16_half_plus<0>(a[0], c0));
-            const float d1 = f16_half_plus<1>(b[0], f16_half_plus<1>(a[0], c0));
-            const float d2 = f16_half_plus<0>(b[1], f16_half_plus<0>(a[1], c0));
-            const float d3 = f16_half_plus<1>(b[1], f16_half_plus<1>(a[1], c0));
-            if constexpr (RES == 3) {
-              v4.x = fmaf(d0, st.y * g4.x, v4.x); v4.y = fmaf(d1, st.y * g4.y, v4.y);
-              v4.z = fmaf(d2, st.y * g4.z, v4.z); v4.w = fmaf(d3, st.y * g4.w, v4.w);
-            } else {
-              v4.x += d0; v4.y += d1; v4.z += d2; v4.w += d3;
-            }
-          } else if constexpr (RES_PLANES) {
-            const u32x2 a = rh[t % RR][g], b = rl[t % RR][g];
-            float4 x4 = make_float4(
-                p16_to_f32((p16_t)(a[0] & 0xffffu)) + p16_to_f32((p16_t)(b[0] & 0xffffu)),
-                p16_to_f32((p16_t)(a[0] >> 16)) + p16_to_f32((p16_t)(b[0] >> 16)),
-                p16_to_f32((p16_t)(a[1] & 0xffffu)) + p16_to_f32((p16_t)(b[1] & 0xffffu)),
-                p16_to_f32((p16_t)(a[1] >> 16)) + p16_to_f32((p16_t)(b[1] >> 16)));
-            if constexpr (RES == 3) {   // the residual is LayerNorm(x), rebuilt from x's planes and its row statistics
-              x4.x = (x4.x - st.x) * st.y * g4.x; x4.y = (x4.y - st.x) * st.y * g4.y;   // (+ beta: in bb4)
-              x4.z = (x4.z - st.x) * st.y * g4.z; x4.w = (x4.w - st.x) * st.y * g4.w;
-            }
-            v4.x += x4.x; v4.y += x4.y; v4.z += x4.z; v4.w += x4.w;
+        if constexpr (RES == 1) {
+          const f32x4 q4 = rr[t % RR][g];
+          v4.x += q4[0]; v4.y += q4[1]; v4.z += q4[2]; v4.w += q4[3];
+        } else if constexpr (RES_PLANES && kSplitF16) {
+          // x = hi + lo (RES == 3: minus the row mean, times rstd * gamma; beta rides in the bias vector bb4): the planes are
+          // converted inside the adds (common.h f16_half_plus), the mean leaves before anything is scaled
+          const u32x2 a = rh[t % RR][g], b = rl[t % RR][g];
+          const float c0 = RES == 3 ? -st.x : 0.f;
+          const float d0 = f16_half_plus<0>(b[0], f16_half_plus<0>(a[0], c0));
+          const float d1 = f16_half_plus<1>(b[0], f16_half_plus<1>(a[0], c0));
+          const float d2 = f16_half_plus<0>(b[1], f16_half_plus<0>(a[1], c0));
+          const float d3 = f16_half_plus<1>(b[1], f16_half_plus<1>(a[1], c0));
+          if constexpr (RES == 3) {
+            v4.x = fmaf(d0, st.y * g4.x, v4.x); v4.y = fmaf(d1, st.y * g4.y, v4.y);
+            v4.z = fmaf(d2, st.y * g4.z, v4.z); v4.w = fmaf(d3, st.y * g4.w, v4.w);
+          } else {
+            v4.x += d0; v4.y += d1; v4.z += d2; v4.w += d3;
           }
+        } else if constexpr (RES_PLANES) {
+          const u32x2 a = rh[t % RR][g], b = rl[t % RR][g];
+          float4 x4 = make_float4(
+              p16_to_f32((p16_t)(a[0] & 0xffffu)) + p16_to_f32((p16_t)(b[0] & 0xffffu)),
+              p16_to_f32((p16_t)(a[0] >> 16)) + p16_to_f32((p16_t)(b[0] >> 16)),
+              p16_to_f32((p16_t)(a[1] & 0xffffu)) + p16_to_f32((p16_t)(b[1] & 0xffffu)),
+              p16_to_f32((p16_t)(a[1] >> 16)) + p16_to_f32((p16_t)(b[1] >> 16)));
+          if constexpr (RES == 3) {   // the residual is LayerNorm(x), rebuilt from x's planes and its row statistics
+            x4.x = (x4.x - st.x) * st.y * g4.x; x4.y = (x4.y - st.x) * st.y * g4.y;   // (+ beta: in bb4)
+            x4.z = (x4.z - st.x) * st.y * g4.z; x4.w = (x4.w - st.x) * st.y * g4.w;
+          }
+          v4.x += x4.x; v4.y += x4.y; v4.z += x4.z; v4.w += x4.w;
         }
         if constexpr (OSTAT) {   // partial (sum, centred sum of squares) of this row over the wave's 32 columns
           const float s1 = sum_lanes8((v4.x + v4.y) + (v4.z + v4.w));
@@ -1470,39 +1102,36 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
           const float m2 = sum_lanes8((dx * dx + dy * dy) + (dz * dz + dw * dw));
           if ((lane_e & 7) == 0) part[row_in_tile] = make_float2(s1, m2);
         }
-        if (!(ABL & 1)) {
-          if constexpr (CLIP_OUT) split4_store_clip(w_oh, w_ol, voff0 + (uint32_t)(t * 32 + 8 * g) * pitch2, v4);
-          if constexpr (EMBED || OUT_F32) {
-            const int m = m0 + row_in_tile;
-            if (m < m_end && n4 < N) {  // N % 4 == 0
-              if constexpr (EMBED) {
-                const int bb = m / ep.emb_T, tt = m - bb * ep.emb_T;
-                for (int br = 0; br < ep.emb_nbranch; ++br) {
-                  const size_t o = ((size_t)(br * ep.emb_B + bb) * (ep.emb_T + 1) + 1 + tt) * ep.ld + n4;
-                  split4_store(ep.oh + o, ep.ol + o, v4);
-                }
-              } else {
-                st4(ep.out + (size_t)m * ep.ld + n4, v4);
+        if constexpr (CLIP_OUT) split4_store_clip(w_oh, w_ol, voff0 + (uint32_t)(t * 32 + 8 * g) * pitch2, v4);
+        if constexpr (EMBED || OUT_F32) {
+          const int m = m0 + row_in_tile;
+          if (m < m_end && n4 < N) {  // N % 4 == 0
+            if constexpr (EMBED) {
+              const int bb = m / ep.emb_T, tt = m - bb * ep.emb_T;
+              for (int br = 0; br < ep.emb_nbranch; ++br) {
+                const size_t o = ((size_t)(br * ep.emb_B + bb) * (ep.emb_T + 1) + 1 + tt) * ep.ld + n4;
+                split4_store(ep.oh + o, ep.ol + o, v4);
               }
+            } else {
+              st4(ep.out + (size_t)m * ep.ld + n4, v4);
             }
           }
         }
       });
     }
-    }   // epilogue scope
-    });
+    }();   // epilogue scope
     if constexpr (OSTAT && !OUT_QKV) {   // rows x column blocks partials -> one (sum, M2) pair per row and column tile
         const int m_end = min(M, m0 + rows_per_tile);
         wg_barrier();
         if (tid < X3_TM && m0 + tid < m_end) {
-          const float2* pp = reinterpret_cast<const float2*>(lds + x3_part_base(NBLK, RINGN));
+          const float2* pp = reinterpret_cast<const float2*>(lds + x3_part_base(RINGN));
           float s1 = 0.f;
 #pragma unroll
-          for (int w8 = 0; w8 < NBLK; ++w8) s1 += pp[w8 * X3_TM + tid].x;
+          for (int w8 = 0; w8 < X3_NWAVE; ++w8) s1 += pp[w8 * X3_TM + tid].x;
           const float mt = s1 * (1.0f / X3_TN);     // OSTAT launches have N % X3_TN == 0: every block contributes 32 columns
           float m2 = 0.f;
 #pragma unroll
-          for (int w8 = 0; w8 < NBLK; ++w8) {
+          for (int w8 = 0; w8 < X3_NWAVE; ++w8) {
             const float2 v = pp[w8 * X3_TM + tid];
             const float dm = v.x * (1.0f / 32.0f) - mt;
             m2 += v.y + 32.0f * dm * dm;
@@ -1510,15 +1139,6 @@ __global__ __launch_bounds__(64 * WAVES, NCB == 2 ? 1 : 2) void gemm_x3_kernel(X
           *reinterpret_cast<float2*>(ep.ostat + ((size_t)(m0 + tid) * tiles_n + n0 / X3_TN) * 2) = make_float2(s1, m2);
         }
       }
-#ifdef MDM_X3_DBG
-    if constexpr ((ABL & 128) != 0) {
-      const unsigned long long t2 = x3_now();
-      if (tid == 0) {
-        atomicAdd(&g_x3_dbg[0], dbg_w0); atomicAdd(&g_x3_dbg[1], dbg_w1); atomicAdd(&g_x3_dbg[2], dbg_t1 - dbg_t0);
-        atomicAdd(&g_x3_dbg[3], t2 - dbg_t1); atomicAdd(&g_x3_dbg[4], 1ULL); atomicAdd(&g_x3_dbg[5], (unsigned long long)nk); atomicAdd(&g_x3_dbg[6], dbg_bar);
-      }
-    }
-#endif
   }
   wait_vmem_all();  // the stream's last (unused) LDS-DMA stage must land before this workgroup's LDS is released
 }
@@ -1531,10 +1151,9 @@ inline int x3_rows_per_tile(int M, int seq_len) {
   return X3_TM;
 }
 
-// persistent grid: `per_cu` workgroups per CU (4-wave: two -- 60 KB of LDS and <= 256 VGPRs each; 8-wave: one)
-inline int x3_grid_limit(int per_cu) {
+// persistent grid: one workgroup per CU
+inline int x3_grid_limit() {
 #ifdef MDM_EMU
-  (void)per_cu;
   return 3;  // small, so that the emulator exercises the tile roll-over paths
 #else
   static int cus_of[kMaxDevices] = {};   // per device ordinal: a process may drive several GPUs
@@ -1545,235 +1164,83 @@ inline int x3_grid_limit(int per_cu) {
     if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
     if (cus <= 0) cus = 256;
   }
-  int wgs = per_cu * cus / 8 * 8;  // xcd_remap keeps a workgroup on one XCD only if the stride is a multiple of 8
-#ifdef MDM_PROBES   // lab/probes/two_chains.py: two half-batch chains share the chip, each launch takes 1 / div of the CUs
-  static const int div = [] { const char* e = getenv("MDM_X3_GRID_DIV"); return e != nullptr && atoi(e) > 1 ? atoi(e) : 1; }();
-  wgs = wgs / div / 8 * 8;
-#endif
+  const int wgs = cus / 8 * 8;  // xcd_remap keeps a workgroup on one XCD only if the stride is a multiple of 8
   return wgs > 0 ? wgs : 8;
 #endif
 }
 
-// workgroup shape used by the launchers below: 8 waves (default: whole-bench A/B on one box 307 vs 302 motions/s) or 4
-// (mdm_debug_set(2, waves) / MDM_X3_WAVES for A/B probes)
-#ifdef MDM_PROBES
-inline int& x3_waves_setting() {
-  static int waves = [] {
-    const char* e = getenv("MDM_X3_WAVES");   // A/B runs of whole benchmarks
-    return (e != nullptr && e[0] == '4') ? 4 : 8;
-  }();
-  return waves;
-}
-#else
-inline int x3_waves_setting() { return 8; }   // the 4-wave form is compiled into the probe library only
-#endif
-
-template <int WAVES, int ACT, int RES, bool OUT_F32, bool OUT_PLANES, bool OUT_QKV, int ABL, bool FOLD = false,
-          bool OSTAT = false, bool EMBED = false, bool T16 = false, bool F6 = false, bool PIPE = false, int NCB = 1,
-          bool M16 = false, bool PAIR = false>
+template <int ACT, int RES, unsigned FLAGS>
 inline int launch_gemm_x3_w(const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N, int K,
                                 int rpt, hipStream_t stream) {
-  constexpr int NBLK = WAVES * NCB;          // 32-column blocks per tile: the LDS layout is per block
-  constexpr int TN = 32 * NBLK;
-  constexpr bool LN = FOLD || OSTAT || RES == 3;
+  constexpr bool T16 = (FLAGS & X3_T16) != 0, PIPE = (FLAGS & X3_PIPE) != 0, PAIR = (FLAGS & X3_PAIR) != 0;
+  constexpr bool LN = (FLAGS & (X3_FOLD | X3_OSTAT)) != 0 || RES == 3;
   constexpr int RINGN = PIPE ? X3_PIPE_RING : X3_A_RING;
-  const int tiles_m = (M + rpt - 1) / rpt, tiles_n = (N + TN - 1) / TN;
+  const int tiles_m = (M + rpt - 1) / rpt, tiles_n = (N + X3_TN - 1) / X3_TN;
   const int total = tiles_m * tiles_n;
-  static_assert(!(F6 && T16), "the f16f6 k-loop has no 16-row sub-tile yet");
-  auto kfn = &gemm_x3_kernel<WAVES, ACT, RES, OUT_F32, OUT_PLANES, OUT_QKV, ABL, FOLD, OSTAT, EMBED, T16, F6, PIPE, NCB, M16, PAIR>;
+  auto kfn = &gemm_x3_kernel<ACT, RES, FLAGS>;
   if (T16 && rpt > X3_TM - 16) return -2;
   if (PAIR && (rpt + 1 > X3_TM - 16 || ep.pair_B < 1 || M != ep.pair_B * rpt)) return -2;   // tile row S must exist; one tile per sample
   if (PIPE && (K / X3_BK) % 2 != 0) return -2;   // the pipelined k-loop is unrolled over step pairs
   if (!x3_has_col_scale(ACT, RES) && ep.scale_cols > 0) return -2;   // (this instantiation compiles the column scale out)
 #ifndef MDM_EMU
-  if (x3_lds_bytes(NBLK, LN, RINGN) > 65536) {
+  {   // every form needs more than the 64 KB a kernel gets unasked
     static bool configured[kMaxDevices] = {};  // per instantiation and device (the attribute belongs to the device's code object)
-    if (const int rc = rt_dyn_lds_once(kfn, x3_lds_bytes(NBLK, LN, RINGN), configured, stream)) return rc;
+    if (const int rc = rt_dyn_lds_once(kfn, x3_lds_bytes(LN, RINGN), configured, stream)) return rc;
   }
 #endif
-  const int grid = std::min(total, x3_grid_limit((WAVES == 4 && NCB == 1) ? 2 : 1));
-  MDM_LAUNCH(kfn, dim3(grid), dim3(64 * WAVES), x3_lds_bytes(NBLK, LN, RINGN), stream, A, W, ep, M, N, K, rpt, tiles_n, total);
+  const int grid = std::min(total, x3_grid_limit());
+  MDM_LAUNCH(kfn, dim3(grid), dim3(64 * X3_NWAVE), x3_lds_bytes(LN, RINGN), stream, A, W, ep, M, N, K, rpt, tiles_n, total);
   return 0;
 }
 
-// MDM_X3_WIDE=1 (probe library only; read per launch) selects the four-wave, 64-columns-per-wave form of the pipelined loop --
-// built, parity-green on the MI355X and 12 % slower over the whole loop (323 vs 367 motions/s): profiles/r04d_wide.md
-inline bool x3_wide_setting() {
-#ifdef MDM_PROBES
-  const char* e = getenv("MDM_X3_WIDE");
-  return e != nullptr && e[0] == '1';
-#else
-  return false;
-#endif
-}
-
-// The pipelined k-loop (PIPE) is the default wherever it exists (208-row tiles, an even number of 32-deep k steps);
-// MDM_X3_PIPE=0 selects the step-synchronous loop for same-box A/B runs.
-inline bool x3_pipe_setting(int kind = 0) {
-#ifndef MDM_PROBES
-  (void)kind;
-  return true;      // (the product library reads no environment variable)
-#else
-  static const bool on = [] {
-    const char* e = getenv("MDM_X3_PIPE");
-    return !(e != nullptr && e[0] == '0');
-  }();
-  // MDM_X3_PIPE_KINDS: bit k = GEMM kind k of launch_gemm_x3_ln (0 in_proj, 1 out_proj layer 0, 2 out_proj / linear2,
-  // 3 linear1, 4 OutputProcess), bit 5 = layer 0's in_proj; default: all -- bisection of a misbehaving instantiation
-  static const int kinds = [] {
-    const char* e = getenv("MDM_X3_PIPE_KINDS");
-    return e != nullptr ? atoi(e) : 0x3f;
-  }();
-  return on && ((kinds >> kind) & 1);
-#endif
-}
-
-// The GEMMs of the folded-LayerNorm encoder (8-wave workgroups only):
+// The GEMMs of the folded-LayerNorm encoder:
 //   kind 0  in_proj, A = pre-norm sum           FOLD -> attention operand planes
 //   kind 1  out_proj of layer 0                 residual = plain planes, writes planes + row statistics
 //   kind 2  out_proj (l >= 1) / linear2         residual = LayerNorm rebuilt from planes, writes planes + row statistics
 //   kind 3  linear1                             FOLD + GELU -> planes
 //   kind 4  OutputProcess                       FOLD -> fp32
 //   kind 5  InputProcess                        + positional rows, planes to the token rows of every branch (EMBED)
-// WIDE (round 4): the pipelined loop as four waves x 64 columns, one wave per SIMD (kernel header, NCB = 2)
-// M16 (round 7): the pipelined loop on 16x16x32 MFMAs (kernel header) -- the product's pipelined form
-template <bool T16, bool PIPE = false, bool WIDE = false, bool M16 = false>
+// TILE: the tile form (X3_T16, X3_PIPE), which launch_gemm_x3_ln chooses by shape
+template <unsigned TILE>
 inline int launch_gemm_x3_ln_t(int kind, const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N,
                                    int K, int rpt, hipStream_t s) {
-#ifdef MDM_PROBES   // (measured 12-18 % slower per launch, profiles/r04d_wide.md: instantiated in the probe library only)
-  if constexpr (WIDE) {
-    switch (kind) {
-      case 0: return launch_gemm_x3_w<4, ACT_NONE, 0, false, false, true, 0, true, false, false, T16, false, PIPE, 2>(A, W, ep, M, N, K, rpt, s);
-      case 1: return launch_gemm_x3_w<4, ACT_NONE, 2, false, true, false, 0, false, true, false, T16, false, PIPE, 2>(A, W, ep, M, N, K, rpt, s);
-      case 2: return launch_gemm_x3_w<4, ACT_NONE, 3, false, true, false, 0, false, true, false, T16, false, PIPE, 2>(A, W, ep, M, N, K, rpt, s);
-      case 3: return launch_gemm_x3_w<4, ACT_GELU, 0, false, true, false, 0, true, false, false, T16, false, PIPE, 2>(A, W, ep, M, N, K, rpt, s);
-      case 4: return launch_gemm_x3_w<4, ACT_NONE, 0, true, false, false, 0, true, false, false, T16, false, PIPE, 2>(A, W, ep, M, N, K, rpt, s);
-      default: return -2;
-    }
-  }
-#endif
   switch (kind) {
-    case 0: return launch_gemm_x3_w<8, ACT_NONE, 0, false, false, true, 0, true, false, false, T16, false, PIPE, 1, M16>(A, W, ep, M, N, K, rpt, s);
-    case 1: return launch_gemm_x3_w<8, ACT_NONE, 2, false, true, false, 0, false, true, false, T16, false, PIPE, 1, M16>(A, W, ep, M, N, K, rpt, s);
-    case 2: return launch_gemm_x3_w<8, ACT_NONE, 3, false, true, false, 0, false, true, false, T16, false, PIPE, 1, M16>(A, W, ep, M, N, K, rpt, s);
-    case 3: return launch_gemm_x3_w<8, ACT_GELU, 0, false, true, false, 0, true, false, false, T16, false, PIPE, 1, M16>(A, W, ep, M, N, K, rpt, s);
-    case 4: return launch_gemm_x3_w<8, ACT_NONE, 0, true, false, false, 0, true, false, false, T16, false, PIPE, 1, M16>(A, W, ep, M, N, K, rpt, s);
-    case 5:   // InputProcess: K = 288 is nine steps -- stays on the step-synchronous loop (32x32x16)
-      if constexpr (M16) return -2;
-      return launch_gemm_x3_w<8, ACT_NONE, 1, false, true, false, 0, false, false, true, T16>(A, W, ep, M, N, K, rpt, s);
+    case 0: return launch_gemm_x3_w<ACT_NONE, /*RES*/ 0, X3_OUT_QKV | X3_FOLD | TILE>(A, W, ep, M, N, K, rpt, s);
+    case 1: return launch_gemm_x3_w<ACT_NONE, /*RES*/ 2, X3_OUT_PLANES | X3_OSTAT | TILE>(A, W, ep, M, N, K, rpt, s);
+    case 2: return launch_gemm_x3_w<ACT_NONE, /*RES*/ 3, X3_OUT_PLANES | X3_OSTAT | TILE>(A, W, ep, M, N, K, rpt, s);
+    case 3: return launch_gemm_x3_w<ACT_GELU, /*RES*/ 0, X3_OUT_PLANES | X3_FOLD | TILE>(A, W, ep, M, N, K, rpt, s);
+    case 4: return launch_gemm_x3_w<ACT_NONE, /*RES*/ 0, X3_OUT_F32 | X3_FOLD | TILE>(A, W, ep, M, N, K, rpt, s);
+    case 5:   // InputProcess: K = 288 is nine steps -- always the step-synchronous loop
+      return launch_gemm_x3_w<ACT_NONE, /*RES*/ 1, X3_OUT_PLANES | X3_EMBED | (TILE & X3_T16)>(A, W, ep, M, N, K, rpt, s);
     default: return -2;
   }
 }
-// 208-row tiles (T16) whenever the row extent of a tile fits (S = 197 does); probe library: MDM_X3_T16=0 keeps 224-row tiles
-inline bool x3_t16_setting() {
-#ifdef MDM_PROBES
-  static const bool on = [] {
-    const char* e = getenv("MDM_X3_T16");
-    return !(e != nullptr && e[0] == '0');
-  }();
-  return on;
-#else
-  return true;
-#endif
-}
-// The pipelined loop runs on 16x16x32 MFMAs (M16); probe library: MDM_X3_M32=1 selects the 32x32x16 form for same-box A/B runs
-// (the product library instantiates the 16x16x32 form only)
-inline bool x3_m16_setting() {
-#ifdef MDM_PROBES
-  static const bool on = [] {
-    const char* e = getenv("MDM_X3_M32");
-    return !(e != nullptr && e[0] == '1');
-  }();
-  return on;
-#else
-  return true;
-#endif
-}
+// 208-row tiles whenever the row extent of a tile fits (S = 197 does); on them the pipelined loop wherever it exists (an even
+// number of 32-deep k steps; not InputProcess)
 inline int launch_gemm_x3_ln(int kind, const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N,
                                  int K, int rpt, hipStream_t s) {
-  if (rpt <= X3_TM - 16 && x3_t16_setting()) {
-    if (kind != 5 && (K / X3_BK) % 2 == 0 && x3_pipe_setting(kind)) {
-#ifdef MDM_PROBES
-      if (x3_wide_setting()) return launch_gemm_x3_ln_t<true, true, true>(kind, A, W, ep, M, N, K, rpt, s);
-      if (!x3_m16_setting()) return launch_gemm_x3_ln_t<true, true>(kind, A, W, ep, M, N, K, rpt, s);
-#endif
-      return launch_gemm_x3_ln_t<true, true, false, true>(kind, A, W, ep, M, N, K, rpt, s);
-    }
-    return launch_gemm_x3_ln_t<true>(kind, A, W, ep, M, N, K, rpt, s);
+  if (rpt <= X3_TM - 16) {
+    if (kind != 5 && (K / X3_BK) % 2 == 0) return launch_gemm_x3_ln_t<X3_T16 | X3_PIPE>(kind, A, W, ep, M, N, K, rpt, s);
+    return launch_gemm_x3_ln_t<X3_T16>(kind, A, W, ep, M, N, K, rpt, s);
   }
-  return launch_gemm_x3_ln_t<false>(kind, A, W, ep, M, N, K, rpt, s);
+  return launch_gemm_x3_ln_t<0u>(kind, A, W, ep, M, N, K, rpt, s);
 }
 
-#ifdef MDM_PROBES
-inline int& x3_pipe_probe() { static int on = 0; return on; }
-#endif
-
-template <int ACT, int RES, bool OUT_F32, bool OUT_PLANES, bool OUT_QKV, int ABL = 0>
-inline int launch_gemm_x3_t(const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N, int K,
-                                int rpt, hipStream_t stream) {
-#ifdef MDM_PROBES
-  if (x3_waves_setting() == 4)
-    return launch_gemm_x3_w<4, ACT, RES, OUT_F32, OUT_PLANES, OUT_QKV, ABL>(A, W, ep, M, N, K, rpt, stream);
-#endif
-  return launch_gemm_x3_w<8, ACT, RES, OUT_F32, OUT_PLANES, OUT_QKV, ABL>(A, W, ep, M, N, K, rpt, stream);
-}
-
-// runtime (act, res, outputs) -> one of the instantiations the encoder needs
+// runtime (act, res, outputs) -> one of the instantiations the encoder needs (224-row tiles, step-synchronous loop)
 inline int launch_gemm_x3(const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N, int K, int act,
-                              int seq_len, hipStream_t s, int ablate = 0) {
+                              int seq_len, hipStream_t s) {
   const bool res = ep.res != nullptr, f32 = ep.out != nullptr, pl = ep.oh != nullptr;
   const int rpt = x3_rows_per_tile(M, seq_len);
   if (ep.resh != nullptr) {  // residual stream held as planes (the model's f16x3 mode)
-    if (ablate == 0 && act == ACT_NONE && !res && f32 && !pl)
-      return launch_gemm_x3_t<ACT_NONE, 2, true, false, false>(A, W, ep, M, N, K, rpt, s);
+    if (act == ACT_NONE && !res && f32 && !pl) return launch_gemm_x3_w<ACT_NONE, /*RES*/ 2, X3_OUT_F32>(A, W, ep, M, N, K, rpt, s);
     return -2;
   }
-#ifdef MDM_PROBES
-  // mdm_debug_set(6, p): the plain fp32-out variant on 208-row (T16) tiles of 197-token sequences -- p = 1: the PIPELINED
-  // k-loop, p = 2: the step-synchronous one -- with the ablation codes both support (1 no epilogue stores, 2 no loads after
-  // the prologue, 4 no MFMAs, and their sums): tools/gemm_probe_pipe.py
-  if (x3_pipe_probe() != 0 && act == ACT_NONE && !res && f32 && !pl && M % 197 == 0 && (K / X3_BK) % 2 == 0) {
-#define X3_PIPE_PROBE_CASE(c) case c: return x3_pipe_probe() == 1 \
-      ? launch_gemm_x3_w<8, ACT_NONE, 0, true, false, false, c, false, false, false, true, false, true>(A, W, ep, M, N, K, 197, s) \
-      : launch_gemm_x3_w<8, ACT_NONE, 0, true, false, false, c, false, false, false, true, false, false>(A, W, ep, M, N, K, 197, s);
-    switch (ablate) {
-      X3_PIPE_PROBE_CASE(0) X3_PIPE_PROBE_CASE(1) X3_PIPE_PROBE_CASE(2) X3_PIPE_PROBE_CASE(3) X3_PIPE_PROBE_CASE(4)
-      X3_PIPE_PROBE_CASE(5) X3_PIPE_PROBE_CASE(6) X3_PIPE_PROBE_CASE(7)
-      default: return -2;
-    }
-#undef X3_PIPE_PROBE_CASE
-  }
-  if (ablate != 0) {  // profiling experiments (mdm_debug_set): only the plain fp32-out variant is instantiated
-    if (!(act == ACT_NONE && !res && f32 && !pl)) return -2;
-    switch (ablate) {
-      case 1: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 1>(A, W, ep, M, N, K, rpt, s);
-      case 2: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 2>(A, W, ep, M, N, K, rpt, s);
-      case 3: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 3>(A, W, ep, M, N, K, rpt, s);
-      case 4: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 4>(A, W, ep, M, N, K, rpt, s);
-      case 8: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 8>(A, W, ep, M, N, K, rpt, s);
-      case 16: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 16>(A, W, ep, M, N, K, rpt, s);
-      case 32: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 32>(A, W, ep, M, N, K, rpt, s);
-      case 64: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 64>(A, W, ep, M, N, K, rpt, s);
-      case 128: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 128>(A, W, ep, M, N, K, rpt, s);
-      case 256: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 256>(A, W, ep, M, N, K, rpt, s);
-      // decomposition of the no-MFMA floor: 5 = 4|1 (also no stores), 6 = 4|2 (also no loads), 7 = 4|2|1, 68 = 4|64 (half the reads)
-      case 5: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 5>(A, W, ep, M, N, K, rpt, s);
-      case 6: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 6>(A, W, ep, M, N, K, rpt, s);
-      case 7: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 7>(A, W, ep, M, N, K, rpt, s);
-      case 68: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 68>(A, W, ep, M, N, K, rpt, s);
-      case 9: return launch_gemm_x3_t<ACT_NONE, 0, true, false, false, 9>(A, W, ep, M, N, K, rpt, s);
-      default: return -2;
-    }
-  }
-#else
-  if (ablate != 0) return -2;
-#endif
-  if (act == ACT_NONE && !res && f32 && !pl) return launch_gemm_x3_t<ACT_NONE, 0, true, false, false>(A, W, ep, M, N, K, rpt, s);
-  if (act == ACT_NONE && res && f32 && !pl) return launch_gemm_x3_t<ACT_NONE, 1, true, false, false>(A, W, ep, M, N, K, rpt, s);
-  if (act == ACT_GELU && !res && !f32 && pl) return launch_gemm_x3_t<ACT_GELU, 0, false, true, false>(A, W, ep, M, N, K, rpt, s);
-  if (act == ACT_GELU && !res && f32 && !pl) return launch_gemm_x3_t<ACT_GELU, 0, true, false, false>(A, W, ep, M, N, K, rpt, s);
-  if (act == ACT_GELU && res && f32 && !pl) return launch_gemm_x3_t<ACT_GELU, 1, true, false, false>(A, W, ep, M, N, K, rpt, s);
-  if (act == ACT_SILU && !res && f32 && !pl) return launch_gemm_x3_t<ACT_SILU, 0, true, false, false>(A, W, ep, M, N, K, rpt, s);
+  if (act == ACT_NONE && !res && f32 && !pl) return launch_gemm_x3_w<ACT_NONE, /*RES*/ 0, X3_OUT_F32>(A, W, ep, M, N, K, rpt, s);
+  if (act == ACT_NONE && res && f32 && !pl) return launch_gemm_x3_w<ACT_NONE, /*RES*/ 1, X3_OUT_F32>(A, W, ep, M, N, K, rpt, s);
+  if (act == ACT_GELU && !res && !f32 && pl) return launch_gemm_x3_w<ACT_GELU, /*RES*/ 0, X3_OUT_PLANES>(A, W, ep, M, N, K, rpt, s);
+  if (act == ACT_GELU && !res && f32 && !pl) return launch_gemm_x3_w<ACT_GELU, /*RES*/ 0, X3_OUT_F32>(A, W, ep, M, N, K, rpt, s);
+  if (act == ACT_GELU && res && f32 && !pl) return launch_gemm_x3_w<ACT_GELU, /*RES*/ 1, X3_OUT_F32>(A, W, ep, M, N, K, rpt, s);
+  if (act == ACT_SILU && !res && f32 && !pl) return launch_gemm_x3_w<ACT_SILU, /*RES*/ 0, X3_OUT_F32>(A, W, ep, M, N, K, rpt, s);
   return -2;
 }
 
@@ -1782,24 +1249,16 @@ inline int launch_gemm_x3(const X3Operand& A, const X3Weights& W, const X3Epilog
 inline int launch_gemm_f16f6(const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N, int K, int act,
                              hipStream_t s) {
   const bool res = ep.res != nullptr;
-  if (act == ACT_NONE && !res && x3_waves_setting() == 4)   // A/B probes: two independent 4-wave workgroups per CU
-    return launch_gemm_x3_w<4, ACT_NONE, 0, true, false, false, 0, false, false, false, false, true>(A, W, ep, M, N, K, X3_TM, s);
-  if (act == ACT_NONE && !res)
-    return launch_gemm_x3_w<8, ACT_NONE, 0, true, false, false, 0, false, false, false, false, true>(A, W, ep, M, N, K, X3_TM, s);
-  if (act == ACT_NONE && res)
-    return launch_gemm_x3_w<8, ACT_NONE, 1, true, false, false, 0, false, false, false, false, true>(A, W, ep, M, N, K, X3_TM, s);
-  if (act == ACT_GELU && !res)
-    return launch_gemm_x3_w<8, ACT_GELU, 0, true, false, false, 0, false, false, false, false, true>(A, W, ep, M, N, K, X3_TM, s);
+  if (act == ACT_NONE && !res) return launch_gemm_x3_w<ACT_NONE, /*RES*/ 0, X3_OUT_F32 | X3_F6>(A, W, ep, M, N, K, X3_TM, s);
+  if (act == ACT_NONE && res) return launch_gemm_x3_w<ACT_NONE, /*RES*/ 1, X3_OUT_F32 | X3_F6>(A, W, ep, M, N, K, X3_TM, s);
+  if (act == ACT_GELU && !res) return launch_gemm_x3_w<ACT_GELU, /*RES*/ 0, X3_OUT_F32 | X3_F6>(A, W, ep, M, N, K, X3_TM, s);
   return -2;
 }
 #endif
 
-// Does a guided in_proj launch (2 B sequences of S tokens) take the paired tile (kernel header, PAIR)?  Only the product's
-// pipelined 16x16x32 form has it; everything else runs one tile per sequence.
-inline bool x3_qkv_pairs(int S, int D) {
-  return x3_waves_setting() == 8 && S + 1 <= X3_TM - 16 && x3_t16_setting() && (D / X3_BK) % 2 == 0 && x3_pipe_setting(5) &&
-         !x3_wide_setting() && x3_m16_setting();
-}
+// Does a guided in_proj launch (2 B sequences of S tokens) take the paired tile (kernel header, PAIR)?  Only the pipelined loop
+// has it, and tile row S must exist; everything else runs one tile per sequence.
+inline bool x3_qkv_pairs(int S, int D) { return S + 1 <= X3_TM - 16 && (D / X3_BK) % 2 == 0; }
 
 // in_proj: tokens [nseq*S][D] x W [3D][D] -> the attention operand planes; one sequence per tile (tile row == token).
 // pair_B > 0 (nseq == 2 pair_B, x3_qkv_pairs): one tile per SAMPLE, written to both of its sequences.
@@ -1810,26 +1269,13 @@ inline int launch_gemm_x3_qkv(const X3Operand& A, const X3Weights& W, const X3Ep
     if (nseq != 2 * pair_B || !x3_qkv_pairs(S, D)) return -2;
     X3Epilogue ep2 = ep;
     ep2.pair_B = pair_B;
-    return launch_gemm_x3_w<8, ACT_NONE, 0, false, false, true, 0, false, false, false, true, false, true, 1, true, true>(
-        A, W, ep2, pair_B * S, 3 * D, D, S, s);
+    return launch_gemm_x3_w<ACT_NONE, /*RES*/ 0, X3_OUT_QKV | X3_T16 | X3_PIPE | X3_PAIR>(A, W, ep2, pair_B * S, 3 * D, D, S, s);
   }
-  if (x3_waves_setting() == 8 && S <= X3_TM - 16 && x3_t16_setting()) {
-    if ((D / X3_BK) % 2 == 0 && x3_pipe_setting(5)) {
-#ifdef MDM_PROBES
-      if (x3_wide_setting())
-        return launch_gemm_x3_w<4, ACT_NONE, 0, false, false, true, 0, false, false, false, true, false, true, 2>(A, W, ep, nseq * S,
-                                                                                                                   3 * D, D, S, s);
-      if (!x3_m16_setting())
-        return launch_gemm_x3_w<8, ACT_NONE, 0, false, false, true, 0, false, false, false, true, false, true>(A, W, ep, nseq * S,
-                                                                                                                3 * D, D, S, s);
-#endif
-      return launch_gemm_x3_w<8, ACT_NONE, 0, false, false, true, 0, false, false, false, true, false, true, 1, true>(
-          A, W, ep, nseq * S, 3 * D, D, S, s);
-    }
-    return launch_gemm_x3_w<8, ACT_NONE, 0, false, false, true, 0, false, false, false, true>(A, W, ep, nseq * S, 3 * D, D,
-                                                                                                 S, s);
+  if (S <= X3_TM - 16) {
+    if ((D / X3_BK) % 2 == 0) return launch_gemm_x3_w<ACT_NONE, /*RES*/ 0, X3_OUT_QKV | X3_T16 | X3_PIPE>(A, W, ep, nseq * S, 3 * D, D, S, s);
+    return launch_gemm_x3_w<ACT_NONE, /*RES*/ 0, X3_OUT_QKV | X3_T16>(A, W, ep, nseq * S, 3 * D, D, S, s);
   }
-  return launch_gemm_x3_t<ACT_NONE, 0, false, false, true>(A, W, ep, nseq * S, 3 * D, D, S, s);
+  return launch_gemm_x3_w<ACT_NONE, /*RES*/ 0, X3_OUT_QKV>(A, W, ep, nseq * S, 3 * D, D, S, s);
 }
 
 #endif  // MDM_X3_KERNEL_ONLY

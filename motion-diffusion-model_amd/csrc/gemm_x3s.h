@@ -28,7 +28,7 @@ namespace mdm {
 // MDM_X3S_EPI_AHEAD (default 1; -DMDM_X3S_EPI_AHEAD=0: one round trip per round): the epilogue reads round j+1's patch before it finishes
 // round j (a wave's LDS operations execute in order: read j+1, then write j+2 behind it, one patch).  Same-box A/B, 8 of 8 pairs
 // positive: DiP B = 32 +0.45 %, the 50-step loop at B = 1 / 6 / 10 -0.45 / -0.3 / -0.3 % (profiles/r05j_epilogue_ahead.md); the same
-// change in gemm_x3.h (MDM_X3_EPI_AHEAD) measured neutral on the headline and stays off
+// change in gemm_x3.h measured neutral on the headline and was removed there
 #ifndef MDM_X3S_EPI_AHEAD
 #define MDM_X3S_EPI_AHEAD 1
 #endif
@@ -291,9 +291,7 @@ __global__ __launch_bounds__(64 * X3S_WAVES, 2) void gemm_x3s_kernel(X3Operand A
       if constexpr (NCB == 1) vmem_wait<NW>(wsh[sl], wsl[sl]);
       else vmem_wait<NW>(wsh[sl * 2], wsl[sl * 2], wsh[sl * 2 + 1], wsl[sl * 2 + 1]);
       wait_frags(j_tag, std::integral_constant<int, (j + 1 < NSUB) ? 2 * RT : 0>{});
-#ifndef MDM_EMU
-      __builtin_amdgcn_sched_barrier(0);
-#endif
+      sched_fence();
       // (accumulators interleaved: consecutive MFMAs on different accumulators; every A fragment feeds NCB column blocks)
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb)
@@ -307,9 +305,7 @@ __global__ __launch_bounds__(64 * X3S_WAVES, 2) void gemm_x3s_kernel(X3Operand A
       for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
         for (int t = 0; t < RT; ++t) acc[cb * RT + t] = mfma_p16(fah[j & 1][t], wsh[sl * NCB + cb], acc[cb * RT + t]);
-#ifndef MDM_EMU
-      __builtin_amdgcn_sched_barrier(0);
-#endif
+      sched_fence();
       issue_w(std::integral_constant<int, sl>{}, c * NSUB + j + D);
     });
   }

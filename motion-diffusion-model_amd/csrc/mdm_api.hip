@@ -557,14 +557,14 @@ int mdm_randn(float* out, const float* init, const float* eps, float a, float s,
 
 #ifdef MDM_PROBES
 int mdm_debug_set(int what, int value) {
-  if (what == 0) g_x3_ablate = value;
+  // 0 (GEMM ablations), 2 (4-wave workgroups), 6 (sync / pipe probe), 8 (start delay): experiments of gemm_x3.h that were removed
+  // with their code (lab/README.md) -- refused, so that an old A/B script does not measure the product against itself
+  if (what == 0 || what == 2 || what == 6 || what == 8)
+    return fail(MDM_EINVAL, "mdm_debug_set: code " + std::to_string(what) + " belonged to a gemm_x3.h experiment that has been removed");
   if (what == 1) g_x3_reuse_planes = value;
-  if (what == 2 && (value == 4 || value == 8)) x3_waves_setting() = value;
   if (what == 3) g_ax_ablate = value;
   if (what == 4) g_f6_reference = value;
-  if (what == 8) g_x3_delay = value;
   if (what == 5) g_f6_linear = value;
-  if (what == 6) x3_pipe_probe() = value;
 #ifndef MDM_EMU
   if (what == 9) { x3s_tl_target() = value; x3s_tl_count() = 0; }   // gemm_x3s.h timeline probe: stamp the value-th launch from now
   if (what == 10) { xb_tl_target() = value; xb_tl_count() = 0; }    // xattn_block.h timeline probe
@@ -573,7 +573,7 @@ int mdm_debug_set(int what, int value) {
   return MDM_OK;
 }
 
-int mdm_debug_get(int idx, double* out) {   // ABL & 128 cycle counters of gemm_x3.h; idx < 0 resets them
+int mdm_debug_get(int idx, double* out) {   // timeline stamps of the x3s / xattn / selfattn probes
 #ifndef MDM_EMU
   if (idx >= 300000) {   // selfattn_block.h timeline stamps (read once at idx == 300000, then served from the host copy)
     static std::vector<unsigned long long> tl(8 * SB_TL_WGS);
@@ -602,16 +602,12 @@ int mdm_debug_get(int idx, double* out) {   // ABL & 128 cycle counters of gemm_
     *out = (double)tl[idx - 100];
     return MDM_OK;
   }
-  unsigned long long v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (idx < 0) return hipMemcpyToSymbol(HIP_SYMBOL(g_x3_dbg), v, sizeof(v)) == hipSuccess ? MDM_OK : fail(MDM_EHIP, "mdm_debug_get: reset failed");
-  if (idx >= 8 || out == nullptr) return fail(MDM_EINVAL, "mdm_debug_get: bad argument");
-  if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_x3_dbg), sizeof(v)) != hipSuccess) return fail(MDM_EHIP, "mdm_debug_get: read failed");
-  *out = (double)v[idx];
+  return fail(MDM_EINVAL, "mdm_debug_get: not a timeline index");
 #else
   if (out != nullptr) *out = 0.0;
   (void)idx;
-#endif
   return MDM_OK;
+#endif
 }
 #endif
 
@@ -705,7 +701,7 @@ int mdm_linear_f16f6(const float* in, const float* w, const float* bias, const f
   p16_t* wfh = reinterpret_cast<p16_t*>(base + f6_plane_bytes(M, K));
   p16_t* wfl = reinterpret_cast<p16_t*>(base + f6_plane_bytes(M, K) + align_up(x3_packed_weight_elems(N, K) * 2, 256));
   const F6Planes pw = f6_carve(base + f6_plane_bytes(M, K) + 2 * align_up(x3_packed_weight_elems(N, K) * 2, 256), N, K);
-  // the production skeleton (gemm_x3_kernel<..., F6>) where its epilogues exist; else the one-wave-per-tile reference
+  // the production skeleton (gemm_x3_kernel<..., X3_OUT_F32 | X3_F6>) where its epilogues exist; else the one-wave-per-tile reference
   const bool fast = !g_f6_reference && N % 4 == 0 && ((act == ACT_NONE) || (act == ACT_GELU && res == nullptr));
   if (!g_x3_reuse_planes) {
     MDM_LAUNCH(pack_f16f6_kernel, dim3((M * (K / 32) + 255) / 256), dim3(256), 0, s, in, pa, M, K, K);

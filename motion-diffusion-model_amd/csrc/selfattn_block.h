@@ -305,9 +305,7 @@ __global__ __launch_bounds__(64 * SB_WAVES, 1) void selfattn_block_kernel(SelfAt
       if constexpr (CROSS) vmem_wait<NW>(wsh[sl], wsl[sl]);
       else vmem_wait<NW>(wsh[sl * 3], wsl[sl * 3], wsh[sl * 3 + 1], wsl[sl * 3 + 1], wsh[sl * 3 + 2], wsl[sl * 3 + 2]);
       lds_wait<(j + 1 < SB_NSUB) ? 4 : 0>(fah[j & 1][0], fal[j & 1][0], fah[j & 1][1], fal[j & 1][1]);
-#ifndef MDM_EMU
-      __builtin_amdgcn_sched_barrier(0);
-#endif
+      sched_fence();
       // Q, K: acc = W . x^T (lane = token);  V: acc = x . W^T (lane = d).  Consecutive MFMAs on different accumulators.
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
@@ -333,9 +331,7 @@ __global__ __launch_bounds__(64 * SB_WAVES, 1) void selfattn_block_kernel(SelfAt
           acc[NWB - 1][t] = mfma_p16(fah[j & 1][t], wsh[sl * NWB + NWB - 1], acc[NWB - 1][t]);
         }
       }
-#ifndef MDM_EMU
-      __builtin_amdgcn_sched_barrier(0);
-#endif
+      sched_fence();
       issue_w(std::integral_constant<int, sl>{}, c * SB_NSUB + j + WD);
     });
   }

@@ -214,18 +214,14 @@ __global__ __launch_bounds__(64 * XB_WAVES, 1) void xattn_block_kernel(XattnArgs
       if constexpr (j + 1 < 8) read_frags(std::integral_constant<int, j + 1>{}, 0, c);
       wait_w(std::integral_constant<int, sl>{});
       lds_wait<(j + 1 < 8) ? 2 : 0>(fah[j & 1], fal[j & 1]);
-#ifndef MDM_EMU
-      __builtin_amdgcn_sched_barrier(0);
-#endif
+      sched_fence();
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) acc[cb] = mfma_p16(wsh[sl * NCB + cb], fal[j & 1], acc[cb]);
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) acc[cb] = mfma_p16(wsl[sl * NCB + cb], fah[j & 1], acc[cb]);
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) acc[cb] = mfma_p16(wsh[sl * NCB + cb], fah[j & 1], acc[cb]);
-#ifndef MDM_EMU
-      __builtin_amdgcn_sched_barrier(0);
-#endif
+      sched_fence();
       issue_w(std::integral_constant<int, sl>{}, c * 8 + j + WD);      // (the last WD refills are Wo's first sub-steps)
     });
   }
@@ -388,18 +384,14 @@ __global__ __launch_bounds__(64 * XB_WAVES, 1) void xattn_block_kernel(XattnArgs
       if constexpr (j + 1 < 8) read_frags(std::integral_constant<int, j + 1>{}, IMG, c);
       wait_w(std::integral_constant<int, sl>{});
       lds_wait<(j + 1 < 8) ? 2 : 0>(fah[j & 1], fal[j & 1]);
-#ifndef MDM_EMU
-      __builtin_amdgcn_sched_barrier(0);
-#endif
+      sched_fence();
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) acc[cb] = mfma_p16(wsh[sl * NCB + cb], fal[j & 1], acc[cb]);
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) acc[cb] = mfma_p16(wsl[sl * NCB + cb], fah[j & 1], acc[cb]);
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) acc[cb] = mfma_p16(wsh[sl * NCB + cb], fah[j & 1], acc[cb]);
-#ifndef MDM_EMU
-      __builtin_amdgcn_sched_barrier(0);
-#endif
+      sched_fence();
       issue_w(std::integral_constant<int, sl>{}, NSUBT + c * 8 + j + WD);
     });
   }

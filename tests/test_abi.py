@@ -34,7 +34,8 @@ def test_every_declared_symbol_is_exported(lib):
 
 
 def test_probe_surface_is_not_in_the_production_library(lib):
-    """include/mdm_hip_probe.h (experiment switches, the f16f6 kernel) is exported by libmdm_hip_probe.so only."""
+    """include/mdm_hip_probe.h (experiment switches, the f16f6 kernel) is exported by libmdm_hip_probe.so only; mdm_debug_set
+    refuses the codes of retired experiments."""
     from mdm_amd import _native
     src = open(os.path.join(ROOT, "include", "mdm_hip_probe.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
@@ -45,6 +46,10 @@ def test_probe_surface_is_not_in_the_production_library(lib):
         assert not hasattr(lib.lib, n), f"{n} leaked into the production library"
         assert hasattr(probe.lib, n)
     assert not lib.has_probes and probe.has_probes
+    # switches of gemm_x3.h experiments that were removed with their code are refused, not silently ignored; a live one is accepted
+    for code in (0, 2, 6, 8):
+        assert probe.lib.mdm_debug_set(code, 0) == -1 and b"removed" in probe.lib.mdm_last_error(), code
+    assert probe.lib.mdm_debug_set(1, 0) == 0
 
 
 def test_product_library_reads_no_environment_variable(lib):

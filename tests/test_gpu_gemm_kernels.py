@@ -1,4 +1,4 @@
-"""The GEMM kernels on the MI355X at kernel level -- mdm_linear_x3 (csrc/gemm_x3.h, gemm_x3_kernel<8, ...>: 224-row x 256-column tiles,
+"""The GEMM kernels on the MI355X at kernel level -- mdm_linear_x3 (csrc/gemm_x3.h, gemm_x3_kernel<ACT, RES, X3_OUT_F32>: 224-row x 256-column tiles,
 32 k per step), mdm_linear (csrc/gemm_f32.h: 64x64 and 128x128 tiles, 32 k per step, K % 4 == 0) -- and mdm_layernorm against fp64:
 both sides of every tile edge in M, N and K, six operand regimes, every epilogue, the persistent grid's roll-over, and the memory
 contracts.

@@ -251,21 +251,3 @@ def test_operand_split_is_bit_exact_fp16_hi_plus_lo():
     # (-0.0 vs +0.0 in lo is value-identical: compare values where both are zero, bits elsewhere)
     z = (want_lo == 0) & (lo.view(np.float16) == 0)
     assert np.array_equal(lo[~z], want_lo.view(np.uint16)[~z])
-
-
-def test_wide_form_of_the_pipelined_gemm_matches_reference(golden_dir, sd, monkeypatch, engine_options):
-    """gemm_x3.h NCB = 2 (probe library, MDM_X3_WIDE=1): four waves x 64 columns, one wave per SIMD, accumulators in AGPRs -- the
-    arrangement VERDICT r03 item 1a asked for.  12 % slower over the loop (profiles/r04d_wide.md), so not a product path; this
-    keeps it correct against the reference's forward goldens on the sequence-tile kernel."""
-    from mdm_amd import _native
-    monkeypatch.setenv("MDM_X3_WIDE", "1")       # (an experiment switch of the probe library; the product reads no environment)
-    engine_options(small_gemm_max_seqs=0)
-    g = _g(golden_dir, "fwd_B3_T196")
-    B, T = 3, 196
-    y = synth_y(B, T, seed=int(g["y_seed"]), lengths=list(g["lengths"]))
-    x = torch.randn(B, 263, 1, T, generator=torch.Generator().manual_seed(int(g["x_seed"])))
-    t = torch.from_numpy(g["t"])
-    model, _ = make_pair(sd, 50, DEV, guided=True, native_lib=_native.load_probe())
-    og = model(x.to(DEV), t.to(DEV), y=dict(y))
-    oc = model.model(x.to(DEV), t.to(DEV), y=dict(y))
-    assert maxabs(oc.cpu(), g["out_cond"]) < 3e-5 and maxabs(og.cpu(), g["out_cfg"]) < 1.2e-4

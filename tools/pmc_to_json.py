@@ -18,38 +18,23 @@ src, dst = sys.argv[1], sys.argv[2]
 
 def classify(name):
     """-> (section, key) for the kernels of the sampling loop; the GEMM is told apart by its template arguments
-    <WAVES, ACT, RES, OUT_F32, OUT_PLANES, OUT_QKV, ABL, FOLD, OSTAT, EMBED, T16, F6> read from the END (names arrive
-    truncated on the left)."""
+    <ACT, RES, FLAGS> (csrc/gemm_x3.h X3_* bits) read from the END (names arrive truncated on the left)."""
     name = name.strip().strip("`")
-    if "gemm_x3_kernel" in name or "_x3_kernel<" in name or re.search(r"(true|false)(, (true|false)){4}>", name):
-        args = [a.strip() for a in name[name.rfind("<") + 1:name.rfind(">")].split(",")] if "<" in name else \
-            [a.strip() for a in name[:name.rfind(">")].split(",")]
-        if len(args) >= 11:
-            # round 3 appended a 13th template argument (PIPE): names arrive truncated on the LEFT, so count from the right --
-            # 13 arguments (or 12 + a cut one) are told from 12 by whether the kernel name carries all of <8, ...>
-            full = name[name.rfind("<") + 1:name.rfind(">")].split(",") if "<" in name else []
-            has_pipe = len(full) == 13 or ("<" not in name and os.environ.get("PMC_PIPE_ARG", "1") == "1")
-            tail = args[::-1][1:12] if has_pipe else args[::-1][:11]
-            # round 4 appended a 14th argument (NCB, an integer): the last argument is then a number, PIPE the one before it
-            if args[-1].strip().isdigit() and len(args) >= 13 and args[-2].strip() in ("true", "false"):
-                tail = args[::-1][2:13]
-            # round 7 appended M16 and round 8 PAIR (booleans) behind NCB: the integer is then the second / third argument from the right
-            for behind in (1, 2):
-                if len(args) >= 13 + behind and args[-1 - behind].strip().isdigit() and args[-2 - behind].strip() in ("true", "false"):
-                    tail = args[::-1][2 + behind:13 + behind]
-            f6, t16, embed, ostat, fold, abl, qkv, planes, f32, res, act = tail
-            b = lambda v: v == "true"   # noqa: E731
-            if b(embed):
-                return "gemm", "InputProcess"
-            if b(qkv):
-                return "gemm", "in_proj" if b(fold) else "in_proj_layer0"
-            if b(ostat):
-                return "gemm", "out_proj|linear2" if res == "3" else "out_proj_layer0"
-            if act == "1":
-                return "gemm", "linear1"
-            if b(f32) and b(fold):
-                return "gemm", "OutputProcess"
-            return "gemm", "other<" + ",".join(args[-11:]) + ">"
+    m = re.search(r"(\d+), (\d+), (\d+)u>", name)
+    if m:   # (no other kernel of the library has an unsigned template argument)
+        act, res, flags = (int(g) for g in m.groups())
+        f32, qkv, fold, ostat, embed = (bool(flags >> bit & 1) for bit in (0, 2, 3, 4, 5))
+        if embed:
+            return "gemm", "InputProcess"
+        if qkv:
+            return "gemm", "in_proj" if fold else "in_proj_layer0"
+        if ostat:
+            return "gemm", "out_proj|linear2" if res == 3 else "out_proj_layer0"
+        if act == 1:
+            return "gemm", "linear1"
+        if f32 and fold:
+            return "gemm", "OutputProcess"
+        return "gemm", f"other<{act}, {res}, {flags}u>"
     for pat, k in (("fold_layernorm_kernel", "fold_layernorm (mdm_prepare)"), ("attention_x3_kernel", "attention"), ("pose_to_planes_kernel", "pose_to_planes"), ("layernorm_kernel", "layernorm"),
                    ("outproj_finish_kernel", "outproj_finish"), ("cond_token_kernel", "cond_token")):
         if pat in name:
