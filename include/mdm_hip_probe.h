@@ -14,10 +14,13 @@ extern "C" {
 #endif
 
 /* Process-global switches; value 0 = production behaviour.  what = 1: mdm_linear_x3 reuses the operand planes already in scratch
- * (kernel-only timing); what = 3: attention ablation code; what = 4: mdm_linear_f16f6 on its reference kernel; what = 5: the `f32`
+ * (kernel-only timing); what = 4: mdm_linear_f16f6 on its reference kernel; what = 5: the `f32`
  * mode's encoder GEMMs run unfused on the f16f6 kernel, operands packed per call into a scratch this library allocates itself;
  * what = 9 / 10 / 11: stamp the value-th launch from now of the gemm_x3s.h / xattn_block.h / selfattn_block.h timeline probes.
- * what = 0, 2, 6, 8 selected experiments of gemm_x3.h that were removed with their code: MDM_EINVAL. */
+ * what = 0, 2, 6, 8 selected experiments of gemm_x3.h, what = 3 the timing ablations of attention_x3.h, that were removed with
+ * their code (lab/README.md): MDM_EINVAL.
+ * Environment: the probe library reads MDM_DIP_GROUPS and MDM_CHAIN_FREE (the reproducers of profiles/r03g_dip_groups.md) and no
+ * other variable; the product library reads none. */
 int mdm_debug_set(int what, int value);
 /* Timeline stamps: idx 100.. gemm_x3s.h, 200000.. xattn_block.h, 300000.. selfattn_block.h; any other idx: MDM_EINVAL. */
 int mdm_debug_get(int idx, double* out);

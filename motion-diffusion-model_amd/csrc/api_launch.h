@@ -109,13 +109,10 @@ int launch_attention(Profiler* pf, const float* qkv, float* out, const int* leng
   return launch_attention_args(pf, a, out, nseq, D, H, oh, ol, s);
 }
 
-#ifdef MDM_PROBES
-int g_ax_ablate = 0;   // mdm_debug_set(3, code): timing experiments on the NKT = 7 attention kernel (attention_x3.h ABL)
-#endif
-template <int NKT, int ABL = 0, bool DIRECT = false>
+template <int NKT, bool DIRECT>
 int launch_attention_x3_t(const QkvPlanes& qp, const int* lengths, int nseq, int B, int S, int D, float* out, p16_t* oh,
                           p16_t* ol, hipStream_t s, int lead) {
-  auto k = &attention_x3_kernel<NKT, ABL, DIRECT>;
+  auto k = &attention_x3_kernel<NKT, DIRECT>;
   const size_t lds = attention_x3_lds_bytes(NKT);
   if (int rc = rt_allow_lds(k, lds)) return rc;
   // two workgroups (query halves) per (sequence, head); the item <-> block mapping pairs blocks b and b + 8 (same XCD),
@@ -125,6 +122,19 @@ int launch_attention_x3_t(const QkvPlanes& qp, const int* lengths, int nseq, int
   const int grid = std::min(groups * 16, std::max(16, 2 * x3_grid_limit() / 16 * 16));
   MDM_LAUNCH(k, dim3(grid), dim3(256), lds, s, qp, lengths, S, D, B, lead, out, oh, ol, items);
   return rt_launch_status();
+}
+template <bool DIRECT>
+int launch_attention_x3_nkt(const QkvPlanes& qp, const int* lengths, int nseq, int B, int S, int D, float* out, p16_t* oh,
+                            p16_t* ol, hipStream_t s, int lead) {
+  switch (qp.NKT) {
+    case 1: return launch_attention_x3_t<1, DIRECT>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
+    case 2: return launch_attention_x3_t<2, DIRECT>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
+    case 3: return launch_attention_x3_t<3, DIRECT>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
+    case 4: return launch_attention_x3_t<4, DIRECT>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
+    case 5: return launch_attention_x3_t<5, DIRECT>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
+    case 6: return launch_attention_x3_t<6, DIRECT>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
+    default: return launch_attention_x3_t<7, DIRECT>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
+  }
 }
 
 // split-precision attention on the operand planes written by the in_proj epilogue (or qkv_pack_kernel)
@@ -141,45 +151,9 @@ int launch_attention_x3(Profiler* pf, const QkvPlanes& qp, const int* lengths, i
     MDM_LAUNCH(attention_x3_long_kernel, dim3(nseq * qp.H * nqb), dim3(256), al_x3_lds_bytes(), s, qp, lengths, S, D, B, lead, out, oh, ol, nqb);
     return rt_launch_status();
   }
-  if (direct && out == nullptr && oh != nullptr) {   // planes straight from the accumulators (attention_x3.h DIRECT)
-    switch (qp.NKT) {
-      case 1: return launch_attention_x3_t<1, 0, true>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-      case 2: return launch_attention_x3_t<2, 0, true>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-      case 3: return launch_attention_x3_t<3, 0, true>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-      case 4: return launch_attention_x3_t<4, 0, true>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-      case 5: return launch_attention_x3_t<5, 0, true>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-      case 6: return launch_attention_x3_t<6, 0, true>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-      default: return launch_attention_x3_t<7, 0, true>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-    }
-  }
-  switch (qp.NKT) {
-    case 1: return launch_attention_x3_t<1>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-    case 2: return launch_attention_x3_t<2>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-    case 3: return launch_attention_x3_t<3>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-    case 4: return launch_attention_x3_t<4>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-    case 5: return launch_attention_x3_t<5>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-    case 6: return launch_attention_x3_t<6>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-    default:
-#ifdef MDM_PROBES
-      static const int env_abl = [] { const char* e = getenv("MDM_AX_ABL"); return e != nullptr ? atoi(e) : 0; }();   // whole-bench A/B runs
-      switch (g_ax_ablate != 0 ? g_ax_ablate : env_abl) {
-        case 1: return launch_attention_x3_t<7, 1>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-        case 2: return launch_attention_x3_t<7, 2>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-        case 3: return launch_attention_x3_t<7, 3>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-        case 4: return launch_attention_x3_t<7, 4>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-        case 8: return launch_attention_x3_t<7, 8>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-        case 16: return launch_attention_x3_t<7, 16>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-        case 32: return launch_attention_x3_t<7, 32>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-        case 48: return launch_attention_x3_t<7, 48>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-        case 63: return launch_attention_x3_t<7, 63>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-        case 64: return launch_attention_x3_t<7, 64>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-        case 128: return launch_attention_x3_t<7, 128>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-        case 192: return launch_attention_x3_t<7, 192>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-        default: break;
-      }
-#endif
-      return launch_attention_x3_t<7>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
-  }
+  if (direct && out == nullptr && oh != nullptr)   // planes straight from the accumulators (attention_x3.h DIRECT)
+    return launch_attention_x3_nkt<true>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
+  return launch_attention_x3_nkt<false>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
 }
 
 #ifdef MDM_PROBES
@@ -252,12 +226,7 @@ int launch_linear_lnfold(Profiler* pf, const float* in, int ld_in, const LnFold&
   if (K % 16 != 0 || ld_in % 4 != 0 || N % LN_PART_COLS != 0) return fail(MDM_EINVAL, "linear (LayerNorm fold): bad K / N");
   RowMajorLoader al{in, ld_in, M, K};
   LnLinearEpilogue ep{out, bias, N, act, scale_cols, col_scale, a_ln, colsum, res, res_ln, ostat};
-#ifdef MDM_PROBES   // A/B switch of the probe library: MDM_DEC_FRAGB=0 sends the layer weights through the fp32 loader again
-  static const bool fragb = [] { const char* e = getenv("MDM_DEC_FRAGB"); return e == nullptr || e[0] != '0'; }();
-#else
-  constexpr bool fragb = true;
-#endif
-  if (x3 && wp.hi != nullptr && fragb) {
+  if (x3 && wp.hi != nullptr) {
     X3FragB bl{wp.hi, wp.lo, (N + 31) / 32, K};
     launch_gemm_f32(al, bl, ep, M, N, K, s, true);
   } else {
@@ -306,7 +275,7 @@ struct LnArgs {
   int parts = 1; float inv_dim = 1.f;
   const float* res_f32 = nullptr; int emb_T = 1, emb_B = 1, emb_nbranch = 1;                     // EMBED (kind 5)
   bool small = false;      // the small-row-count kernel (gemm_x3s.h): the whole forward runs on one of the two kernels
-  X3sShape shape{1, 1};    // ... and on ONE tile shape of it (x3s_shape(m->x3s, nseq))
+  X3sShape shape{1};       // ... and on ONE tile shape of it (x3s_shape(m->x3s, nseq))
   int stat_cols = 256;     // columns per partial of astat / rstat (what the PRODUCER's kernel wrote)
 };
 // The latency regime (gemm_x3s.h): a forward of at most MDM_OPT_SMALL_GEMM_MAX_SEQS sequences runs its GEMMs on 32 / 64-row tiles --
@@ -327,12 +296,7 @@ int launch_x3_ln(Profiler* pf, int prof_cat, int kind, X3Operand a, X3Weights w,
                 ln.astat, ln.colsum, ln.rstat, ln.rgamma, ln.rbeta, ln.ostat, ln.parts, ln.inv_dim, ln.emb_T, ln.emb_B,
                 ln.emb_nbranch};
   ep.stat_cols = ln.stat_cols;
-  bool small = ln.small;
-#ifdef MDM_PROBES   // (bisection of a misbehaving instantiation: bit k = GEMM kind k may run on the small kernel; results are wrong
-                    // when producer and consumer of a row-statistics array disagree about their geometry)
-  if (const char* e = getenv("MDM_X3S_KINDS")) small = small && ((atoi(e) >> kind) & 1);
-#endif
-  if (small) {
+  if (ln.small) {
     // rows are grouped by sequence only where the epilogue needs (sequence, token) -- in_proj's Q / K / V^T planes, InputProcess's
     // (sample, frame); every other GEMM tiles its M rows CONTIGUOUSLY: 197 tokens are three 64-row tiles plus one of 5 rows, i.e.
     // a quarter of the workgroups of a sequence-aligned launch would do 8 % of a tile's work (B = 6: 37 row tiles instead of 48)
@@ -340,16 +304,9 @@ int launch_x3_ln(Profiler* pf, int prof_cat, int kind, X3Operand a, X3Weights w,
     const int rc = launch_gemm_x3s(kind, ln.shape, a, w, ep, M, N, K, group_rows, s);
     if (rc == -1 || rc == -3) return lds_fail(rc, "f16x3 linear (small tiles)");
     if (rc == -2) return fail(MDM_EUNSUPPORTED, "f16x3 linear (small tiles): unsupported shape (K must be 288 or a multiple of 256)");
-#if defined(MDM_PROBES) && !defined(MDM_EMU)
-    if (getenv("MDM_X3S_TRACE")) {      // bring-up: which launch faults
-      fprintf(stderr, "[x3s] kind %d M %d N %d K %d launched\n", kind, M, N, K); fflush(stderr);
-      const hipError_t e = hipStreamSynchronize(s);
-      fprintf(stderr, "[x3s] kind %d done: %s\n", kind, hipGetErrorString(e)); fflush(stderr);
-    }
-#endif
     return rt_launch_status();
   }
-  if (kind == 6) {   // layer 0's in_proj without a folded LayerNorm on the sequence-tile kernel (only reached by the bisection switch)
+  if (kind == 6) {   // layer 0's in_proj without a folded LayerNorm on the sequence-tile kernel: trans_dec's sequence-tile route (decoder.h)
     const int rc6 = launch_gemm_x3_qkv(a, w, ep, M / S, S, D, s);
     if (rc6 != 0) return fail(MDM_EUNSUPPORTED, "f16x3 in_proj: launch failed");
     return rt_launch_status();

@@ -198,6 +198,9 @@ struct ChainGuard {
   hipStream_t s;
   explicit ChainGuard(void* stream) : c(g_chain[rt_device_ordinal()]), s(static_cast<hipStream_t>(stream)) {
     c.mu.lock();
+    // The probe library reads TWO environment variables and nothing else: MDM_CHAIN_FREE (here) and MDM_DIP_GROUPS (loops.h) -- they
+    // reproduce the open co-residency issue (profiles/r03g_dip_groups.md).  Every other switch is an option of the handle
+    // (mdm_set_option) or a code of mdm_debug_set; the product library reads none.
 #ifdef MDM_PROBES   // lab/probes/two_chains.py: chains on different streams are NOT ordered against each other (probe library only)
     static const bool chain_free = [] { const char* e = getenv("MDM_CHAIN_FREE"); return e != nullptr && e[0] == '1'; }();
 #else

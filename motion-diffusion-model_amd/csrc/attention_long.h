@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void attention_x3_long_kernel(QkvPlanes P, con
       const float m_new = fmaxf(m_run, mx);
       if (m_new != -INFINITY) {        // (a tile without a valid key before any valid key -- bitmap masks only -- contributes nothing)
         // fp16 planes: the probabilities are split as hi / lo of p * 2^10 (attention_x3.h); the factor cancels in 1 / l
-        const float mref = kSplitF16 ? m_new - 6.931471805599453f : m_new;
+        const float mref = m_new - 6.931471805599453f;
         const float c = (m_run == -INFINITY) ? 0.f : expf(m_run - m_new);
         float psum = 0.f;
 #pragma unroll

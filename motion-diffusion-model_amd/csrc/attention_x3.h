@@ -6,7 +6,7 @@
 // (F.multi_head_attention_forward under nn.TransformerEncoderLayer, model/mdm.py:77-84, :253) and
 // the key-padding mask of mdm.py:241-247.  The exact-fp32 kernel (attention_f32.h) remains the `f32` mode.
 //
-// Operand planes (all 16-bit -- fp16 by default, common.h kSplitF16 --, hi and lo; SP = tokens padded to a multiple of 32, NKT = SP/32):
+// Operand planes (all fp16, hi and lo; SP = tokens padded to a multiple of 32, NKT = SP/32):
 //   Q, K   [nseq][H][SP][128]            row = token, Q pre-scaled by 1/sqrt(128); pad rows (>= S): never read
 //   V^T    [nseq][H][NKT][128][32]       per 32-key tile: row = d, 32 keys of that tile in MFMA ORDER: inside each
 //                                        group of 16 keys, position p holds key (p&3) + 8*((p>>2)&1) + 4*(p>>3).
@@ -56,9 +56,6 @@ constexpr int AX_KMASK_BYTES = 1024;   // per-key additive mask (0 / -inf) of th
 constexpr int ax_lds_bytes(int) { return AX_RING * AX_SLOT + AX_KMASK_BYTES; }
 static_assert(AX_SLOT + 4 * 32 * AX_OST * 4 <= AX_RING * AX_SLOT, "output staging must fit behind ring slot 0");
 
-// ABL (timing experiments only, 0 in production; results are garbage): 1 = no MFMAs, 2 = no LDS fragment reads,
-// 4 = no softmax, 8 = no output staging / stores, 16 = no K / V^T streaming after the prologue, 32 = no per-tile barrier.
-// Results stay CORRECT with: 64 = non-temporal K / V^T LDS-DMA, 128 = non-temporal plane stores (A/B: profiles/r04b_ab.md).
 // DIRECT (round 5; VERDICT r04 item 4, the item-boundary drain): the output leaves the accumulators as 8-byte plane stores
 // (lane = query row, 4 consecutive d per register quad) instead of being staged through ring slots 1-3 -- so those slots are free the
 // moment the item's last tile has been consumed, and the NEXT item's key tiles 1 and 2 are requested right behind the closing
@@ -86,7 +83,7 @@ __device__ __forceinline__ void ax_split4_store_counted(p16_t* hi_p, p16_t* lo_p
   asm volatile("global_store_dwordx2 %0, %1, off" : : "v"(lo_p), "v"(u32x2{l01, l23}) : "memory");
 #endif
 }
-template <int NKT, int ABL = 0, bool DIRECT = false>
+template <int NKT, bool DIRECT>
 __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const int* __restrict__ lengths,
                                                                     int S, int D, int B, int lead, float* __restrict__ out,
                                                                     p16_t* __restrict__ oh, p16_t* __restrict__ ol,
@@ -130,11 +127,11 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
         // nobody wrote; the swizzle still follows the LDS row
         const int key = 32 * t + 4 * idx + (lv >> 4);
         const p16_t* src = (plane ? P.kl : P.kh) + (sh * SP + (size_t)min(key, S - 1)) * AX_HD + (((lv & 15) ^ (key & 15)) * 8);
-        if constexpr ((ABL & 64) != 0) glds16_nt(src, dst); else glds16(src, dst);
+        glds16(src, dst);
       } else {
         const int d = 16 * idx + (lv >> 2);
         const p16_t* src = (plane ? P.vl : P.vh) + ((sh * NKT + (size_t)(t - NKT)) * AX_HD + d) * 32 + (((lv & 3) ^ ((d >> 2) & 3)) * 8);
-        if constexpr ((ABL & 64) != 0) glds16_nt(src, dst); else glds16(src, dst);
+        glds16(src, dst);
       }
     }
   };
@@ -223,9 +220,9 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
       if (carried && active) ax_vm_wait<4 * ahead + kTrk * (AX_NST + (t == 0 ? 16 : 0))>();
       else if (carried) ax_vm_wait<4 * ahead + kTrk * (t == 0 ? 16 : 0)>();
       else wait_vmem_upto<4 * ahead>();
-    } else if constexpr (!(ABL & 16)) wait_vmem_upto<4 * ahead>();
-    if constexpr (!(ABL & 32)) wg_barrier();  // tile t visible to every wave; every wave is done with tile t-1 (whose slot is refilled now)
-    if constexpr (t + 3 < NTILES && !(ABL & 16)) issue_tile(sh, t + 3, lv);
+    } else wait_vmem_upto<4 * ahead>();
+    wg_barrier();  // tile t visible to every wave; every wave is done with tile t-1 (whose slot is refilled now)
+    if constexpr (t + 3 < NTILES) issue_tile(sh, t + 3, lv);
     if constexpr (t == NTILES - 1) {
       // the next item's first key tile (slot 0: its last tenant, tile NTILES-2 or earlier, is consumed) and Q fragments
       // (their registers have been dead since phase 1) travel under this item's last V^T tile and its output phase
@@ -247,7 +244,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
 #endif
         static_for<8 + 2>([&](auto u_tag) __attribute__((always_inline)) {
           constexpr int u = decltype(u_tag)::value;
-          if constexpr (u < 8 && !(ABL & 2)) {
+          if constexpr (u < 8) {
             AX_RD_K(kh[u % 3], 0, u);
             AX_RD_K(kl[u % 3], 1, u);
           }
@@ -256,21 +253,15 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
             constexpr int younger = 2 * ((7 - st) < 2 ? (7 - st) : 2);
             lds_wait<younger>(kh[st % 3], kl[st % 3]);
             sched_fence();
-            if constexpr (ABL & 1) {
-#ifndef MDM_EMU
-              asm volatile("" ::"v"(kl[st % 3]), "v"(kh[st % 3]), "v"(qh[st]), "v"(ql[st]));
-#endif
-            } else {
-              p[t] = mfma_p16(kl[st % 3], qh[st], p[t]);
-              p[t] = mfma_p16(kh[st % 3], ql[st], p[t]);
-              p[t] = mfma_p16(kh[st % 3], qh[st], p[t]);
-            }
+            p[t] = mfma_p16(kl[st % 3], qh[st], p[t]);
+            p[t] = mfma_p16(kh[st % 3], ql[st], p[t]);
+            p[t] = mfma_p16(kh[st % 3], qh[st], p[t]);
             sched_fence();
           }
         });
 #undef AX_RD_K
       }
-      if constexpr (t == NKT - 1 && !(ABL & 4)) {
+      if constexpr (t == NKT - 1) {
         // ---- softmax over keys: lane-local + one cross-half exchange; 1/sum is applied to the output
         float mx = -INFINITY;
         {
@@ -294,7 +285,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
         // fp16 planes: the probabilities are split as hi / lo of p * 2^10 -- free, by lowering the subtracted maximum by
         // 10 ln 2; the factor cancels in 1 / sum.  Unscaled, a typical p ~ 1/S = 0.005 has an fp16-SUBNORMAL lo part
         // (2^-25 absolute = 2^-17 relative): P.V would be the one bf16-class product left in the path.
-        if constexpr (kSplitF16) mx -= 6.931471805599453f;
+        mx -= 6.931471805599453f;
         float sum = 0.f;
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt)
@@ -330,7 +321,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
 #endif
         static_for<8 + 2>([&](auto u_tag) __attribute__((always_inline)) {
           constexpr int u = decltype(u_tag)::value;
-          if constexpr (u < 8 && !(ABL & 2)) {
+          if constexpr (u < 8) {
             AX_RD_V(vh[u % 3], 0, u / 4, u % 4);
             AX_RD_V(vl[u % 3], 1, u / 4, u % 4);
           }
@@ -347,11 +338,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
             sched_fence();
             // a 16-key group wholly past the sequence (only the last one can be) has p == 0 and V^T rows that the in_proj
             // GEMM's 208-row tiles never wrote: skipped, not multiplied
-            if constexpr (ABL & 1) {
-#ifndef MDM_EMU
-              asm volatile("" ::"v"(vl[uv % 3]), "v"(vh[uv % 3]), "v"(ph), "v"(pl));
-#endif
-            } else if (kt < NKT - 1 || s2 == 0 || last_group) {
+            if (kt < NKT - 1 || s2 == 0 || last_group) {
               o[dt] = mfma_p16(vl[uv % 3], ph, o[dt]);
               o[dt] = mfma_p16(vh[uv % 3], pl, o[dt]);
               o[dt] = mfma_p16(vh[uv % 3], ph, o[dt]);
@@ -391,7 +378,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
   // ---- stage this wave's O[32 queries][128 d] in two passes of 64 d (fp32, row stride AX_OST, wave-private) and store
   // coalesced: accumulator rows mfma_row(4g..4g+3, h) are 4 consecutive d
   float* so = reinterpret_cast<float*>(lds + AX_SLOT) + w * (32 * AX_OST);
-  if (active && !(ABL & 8)) {
+  if (active) {
     const size_t obase = (size_t)seq * S * D + head * AX_HD;
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
@@ -412,30 +399,13 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
           const size_t oo = obase + (size_t)qq * D + 64 * pass + 4 * c4;
           if (out != nullptr) st4(out + oo, v);
           if (oh != nullptr) {   // planes for the out_proj f16x3 GEMM
-            if constexpr ((ABL & 128) != 0) {
-#ifndef MDM_EMU
-              uint32_t h01, l01, h23, l23;
-              split2_p16(v.x, v.y, h01, l01);
-              split2_p16(v.z, v.w, h23, l23);
-              __builtin_nontemporal_store(u32x2{h01, h23}, reinterpret_cast<u32x2*>(oh + oo));
-              __builtin_nontemporal_store(u32x2{l01, l23}, reinterpret_cast<u32x2*>(ol + oo));
-#endif
-            } else {
-              split4_store(oh + oo, ol + oo, v);
-            }
+            split4_store(oh + oo, ol + oo, v);
           }
         }
       }
       wave_lds_fence();
     }
   }
-#ifndef MDM_EMU
-  if constexpr ((ABL & 8) != 0) {   // keep the computation alive without the staging / stores
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) asm volatile("" ::"v"(o[dt]));
-    asm volatile("" ::"v"(inv));
-  }
-#endif
   if (!has_next) break;
   vb = vb_next;
   }   // item loop

@@ -55,17 +55,14 @@ template <class KF> inline int rt_dyn_lds_once(KF kfn, int bytes, bool* configur
 }
 #endif
 
-// MDM_EARLY_KERNARGS (default 1; -DMDM_EARLY_KERNARGS=0 is the A/B build): pin the scalar loads of the kernel arguments a kernel's FIRST
+// MDM_KERNARGS_NOW: pin the scalar loads of the kernel arguments a kernel's FIRST
 // vector loads depend on into its entry block.  hipcc sinks part of them behind the first s_waitcnt + the (branchy) tile arithmetic --
 // gemm_x3s_kernel: sizes first, wait, tile index, THEN the operand pointers; selfattn_block_kernel: the plane pointer re-read from the
 // kernarg segment with a run-time offset at its point of use -- i.e. two dependent scalar-memory round trips in front of the first
 // LDS-DMA request of kernels that last 10-30 us.  An empty asm statement that names the values as inputs makes them live at the top, so
 // all s_loads go out in one batch.  Used in the two kernels of the latency regime only (round 6, profiles/r06e_early_kernargs.md: DiP
 // +1.0 % same box, per 40-frame call -1.4 %); the persistent kernels of the headline pay their prologue once per 150-250 us and are left alone.
-#ifndef MDM_EARLY_KERNARGS
-#define MDM_EARLY_KERNARGS 1
-#endif
-#if MDM_EARLY_KERNARGS && !defined(MDM_EMU)
+#ifndef MDM_EMU
 #define MDM_KERNARGS_NOW(...) asm volatile("" ::__VA_ARGS__)
 // a kernel-argument pointer as an opaque SGPR value: `(p ? a.lo : a.hi)` on the raw arguments makes hipcc index the kernarg SEGMENT
 // with a run-time offset (s_load ... s46) -- another dependent scalar-memory round trip at the point of use
@@ -88,36 +85,28 @@ __device__ __forceinline__ f32x16 mfma_f32(float a, float b, f32x16 c) {
 
 // ---------------------------------------------------------------------------------------------
 // The 16-bit element of the split-precision ("x3") operand planes.  DEFAULT: IEEE fp16 ("f16x3": 11 + 11 significant bits per
-// fp32 value).  -DMDM_SPLIT_BF16 builds the round-1 bfloat16 form ("f16x3": 8 + 8 bits, fp32's exponent range) for A/B
-// runs.  Same bytes, same MFMA rate (v_mfma_f32_32x32x16_f16 / _bf16), same kernels: only these helpers differ.
-// Why fp16: on "trained-like" weights (oracle/synth.py synth_state_dict_hostile) the bf16 split is 10x the fp32 reference's own
+// fp32 value).  Round 1's bfloat16 planes (8 + 8 bits, fp32's exponent range; same bytes, same MFMA rate) are gone:
+// on "trained-like" weights (oracle/synth.py synth_state_dict_hostile) the bf16 split is 10x the fp32 reference's own
 // rounding noise, the fp16 split sits AT that noise (tools/precision_probe.py, tools/fold_probe.py).
 // Range: |x| <= 65504; beyond it the split yields inf and the sample NaN (a model whose activations leave fp16's range
 // needs the f32 mode -- the sampler seam checks the result and says so); below 2^-14 the planes keep an absolute
 // precision of 2^-25 (fp16 subnormals -- gfx950's MFMA does not flush them).
 // ---------------------------------------------------------------------------------------------
-#ifdef MDM_SPLIT_BF16
-constexpr bool kSplitF16 = false;
-#else
-constexpr bool kSplitF16 = true;
-#endif
 typedef _Float16 f16_t;
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // WEIGHTS are split as hi / lo of (w * 2^8) and the accumulators scaled back by 2^-8 (exact): nn.Linear weights are O(1/sqrt(K))
 // ~ 0.03, whose lo part (~2^-16) would be an fp16 SUBNORMAL with only ~8 significant bits -- the weight would carry 2^-20
-// instead of 2^-23.  Scaled, lo is a normal number for every |w| >= 2^-11; |w| < 255 keeps hi finite.  (bf16 build: 1.)
-constexpr float kX3WeightScale = kSplitF16 ? 256.f : 1.f;
-constexpr float kX3AccScale = kSplitF16 ? 1.f / 256.f : 1.f;
+// instead of 2^-23.  Scaled, lo is a normal number for every |w| >= 2^-11; |w| < 255 keeps hi finite.
+constexpr float kX3WeightScale = 256.f;
+constexpr float kX3AccScale = 1.f / 256.f;
 
-// v_mfma_f32_32x32x16_{f16,bf16}: lane l supplies 8 consecutive-k elements of row/col (l&31), k-block (l>>5).
+// v_mfma_f32_32x32x16_f16: lane l supplies 8 consecutive-k elements of row/col (l&31), k-block (l>>5).
 __device__ __forceinline__ f32x16 mfma_p16(p16x8 a, p16x8 b, f32x16 c) {
 #ifdef MDM_EMU
-  if constexpr (kSplitF16) return emu::mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c);
-  else return emu::mfma_f32_32x32x16_bf16(a, b, c);
+  return emu::mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c);
 #else
-  if constexpr (kSplitF16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 #endif
 }
 
@@ -146,20 +135,18 @@ __device__ __forceinline__ f32x16 mfma_mx_fp6(i32x8 a, i32x8 b, f32x16 c, int sc
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// v_mfma_f32_16x16x32_{f16,bf16}: lane l supplies 8 consecutive-k elements of row/col (l&15), k-block (l>>4) (k = 8*(l>>4)+e);
+// v_mfma_f32_16x16x32_f16: lane l supplies 8 consecutive-k elements of row/col (l&15), k-block (l>>4) (k = 8*(l>>4)+e);
 // D[reg] is row 4*(l>>4) + reg, column l&15.
 __device__ __forceinline__ f32x4 mfma16_p16(p16x8 a, p16x8 b, f32x4 c) {
 #ifdef MDM_EMU
-  if constexpr (kSplitF16) return emu::mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c);
-  else return emu::mfma_f32_16x16x32_bf16(a, b, c);
+  return emu::mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c);
 #else
-  if constexpr (kSplitF16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 #endif
 }
 
-// Two v_mfma_f32_32x32x16_bf16 operand fragments of the same 32 rows -- w0: k 0-15, w1: k 16-31 -- become the two
-// v_mfma_f32_16x16x32_bf16 fragments over the same 32 k -- w0: rows 0-15, w1: rows 16-31.  As rows of 16 lanes,
+// Two v_mfma_f32_32x32x16_f16 operand fragments of the same 32 rows -- w0: k 0-15, w1: k 16-31 -- become the two
+// v_mfma_f32_16x16x32_f16 fragments over the same 32 k -- w0: rows 0-15, w1: rows 16-31.  As rows of 16 lanes,
 //   in   w0 = [r0-15 k0-7 | r16-31 k0-7 | r0-15 k8-15 | r16-31 k8-15]    w1 = the same with k + 16
 //   v_permlane32_swap (lanes 32-63 of w0 <-> lanes 0-31 of w1), then v_permlane16_swap (odd rows of w0 <-> even rows of w1)
 //   out  w0 = [r0-15 k0-7 | r0-15 k8-15 | r0-15 k16-23 | r0-15 k24-31]   w1 = the same for r16-31
@@ -240,39 +227,21 @@ __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 // ---------------------------------------------------------------------------------------------
-// Split-precision helpers: x = hi + lo, hi = rne16(x), lo = rne16(x - hi)  (fp16: +O(2^-22 |x|); bf16 build: +O(2^-17 |x|)).
+// Split-precision helpers: x = hi + lo, hi = rne16(x), lo = rne16(x - hi)  (+O(2^-22 |x|)).
 // A fp32 product a*w is then carried by three 16-bit MFMA products  ah*wh + ah*wl + al*wh  (the al*wl term is dropped),
 // accumulated in fp32: SURVEY.md section 7 "Precision vs. peak".
 // ---------------------------------------------------------------------------------------------
 typedef unsigned short p16_t;
 
 __host__ __device__ __forceinline__ float p16_to_f32(p16_t b) {
-  if constexpr (kSplitF16) {
-    return (float)__builtin_bit_cast(f16_t, b);
-  } else {
-    const uint32_t u = (uint32_t)b << 16;
-    float f;
-    __builtin_memcpy(&f, &u, 4);
-    return f;
-  }
+  return (float)__builtin_bit_cast(f16_t, b);
 }
 
 __host__ __device__ __forceinline__ p16_t f32_to_p16(float x) {
-  if constexpr (kSplitF16) {
-    // round-to-nearest-even, NOT saturating: a value beyond +-65504 becomes inf and surfaces as NaN in the sample -- loud,
-    // and caught by the sampler seam (gaussian_diffusion.py _check_finite) -- instead of being clamped into a plausible
-    // wrong number.  (A v_med3 clamp per value also cost 1.3 % of the whole loop: profiles/r02_ab.md.)
-    return __builtin_bit_cast(p16_t, (f16_t)x);
-  } else {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_bit_cast(unsigned short, (__bf16)x);   // v_cvt_pk_bf16_f32 (round-to-nearest-even)
-#else
-    uint32_t u;
-    __builtin_memcpy(&u, &x, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (p16_t)(u >> 16);
-#endif
-  }
+  // round-to-nearest-even, NOT saturating: a value beyond +-65504 becomes inf and surfaces as NaN in the sample -- loud,
+  // and caught by the sampler seam (gaussian_diffusion.py _check_finite) -- instead of being clamped into a plausible
+  // wrong number.  (A v_med3 clamp per value also cost 1.3 % of the whole loop: profiles/r02_ab.md.)
+  return __builtin_bit_cast(p16_t, (f16_t)x);
 }
 
 __host__ __device__ __forceinline__ void split_p16(float x, p16_t& hi, p16_t& lo) {
@@ -280,7 +249,7 @@ __host__ __device__ __forceinline__ void split_p16(float x, p16_t& hi, p16_t& lo
   lo = f32_to_p16(x - p16_to_f32(hi));
 }
 
-// Two values -> packed (hi, hi) and (lo, lo) dwords.  On the device (fp16 planes): hi = v_cvt_pk_f16_f32 (a packed CONVERSION),
+// Two values -> packed (hi, hi) and (lo, lo) dwords.  On the device: hi = v_cvt_pk_f16_f32 (a packed CONVERSION),
 // lo = fp16(x - float(hi)) in ONE instruction per value: v_fma_mix{lo,hi}_f16 takes the fp16 half of `hi2` and the fp32 value as
 // mixed-precision sources (hi * -1.0 + x: exact in fp32, then one RNE rounding to fp16) -- bit for bit the value of the two-step form
 // (tests/test_gpu_round4.py::test_operand_split_is_bit_exact...), 3 instructions per pair instead of 6, same speed (366.7 / 366.5 vs
@@ -288,38 +257,29 @@ __host__ __device__ __forceinline__ void split_p16(float x, p16_t& hi, p16_t& lo
 // subtracts on a 2-vector (v_pk_add_f32) -- the one packed fp32 instruction that was left in the product library (4,327 instances)
 // after -fno-slp-vectorize, i.e. the instruction class of the unexplained co-residency corruption (include/mdm_hip.h CONCURRENCY,
 // profiles/r04c_packed_math.md).  tests/test_abi.py disassembles the product library and fails on any v_pk_*_f32.
-// -DMDM_SPLIT_PKSUB builds the two-step form for A/B runs.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void split2_p16(float a, float b, uint32_t& hi2, uint32_t& lo2) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (kSplitF16) {
-    const f32x2 v = {a, b};
-    const f16x2 h = __builtin_convertvector(v, f16x2);       // v_cvt_pk_f16_f32
-    hi2 = __builtin_bit_cast(uint32_t, h);
-#ifndef MDM_SPLIT_PKSUB
-    uint32_t l;
-    // HARDWARE FINDING (round 5, profiles/r05m_fma_mix_hazard.md): a v_mfma that reads a register written by v_fma_mix{lo,hi}_f16 needs
-    // wait states in between, and hipcc's hazard recognizer does not look into inline asm -- it put the MFMA one instruction behind the
-    // pair, and xattn_block_kernel<4, 3> (70 memory tokens: its K / V / P fragments go from this split straight into MFMAs) returned
-    // 7e-2 errors that changed from run to run; every other kernel got its distance by luck of the schedule.  Two wait states behind
-    // the pair cure it (bisected on the MI355X: the two-step form and this form pass, the bare pair and the pair as one statement fail).
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l) : "v"(hi2), "v"(a));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\ts_nop 1" : "+v"(l) : "v"(hi2), "v"(b));
-    lo2 = l;
+  const f32x2 v = {a, b};
+  const f16x2 h = __builtin_convertvector(v, f16x2);       // v_cvt_pk_f16_f32
+  hi2 = __builtin_bit_cast(uint32_t, h);
+  uint32_t l;
+  // HARDWARE FINDING (round 5, profiles/r05m_fma_mix_hazard.md): a v_mfma that reads a register written by v_fma_mix{lo,hi}_f16 needs
+  // wait states in between, and hipcc's hazard recognizer does not look into inline asm -- it put the MFMA one instruction behind the
+  // pair, and xattn_block_kernel<4, 3> (70 memory tokens: its K / V / P fragments go from this split straight into MFMAs) returned
+  // 7e-2 errors that changed from run to run; every other kernel got its distance by luck of the schedule.  Two wait states behind
+  // the pair cure it (bisected on the MI355X: the two-step form and this form pass, the bare pair and the pair as one statement fail).
+  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l) : "v"(hi2), "v"(a));
+  asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\ts_nop 1" : "+v"(l) : "v"(hi2), "v"(b));
+  lo2 = l;
 #else
-    const f32x2 r = v - __builtin_convertvector(h, f32x2);   // v_pk_add_f32
-    const f16x2 l = __builtin_convertvector(r, f16x2);
-    lo2 = __builtin_bit_cast(uint32_t, l);
-#endif
-    return;
-  }
-#endif
   p16_t h0, l0, h1, l1;
   split_p16(a, h0, l0);
   split_p16(b, h1, l1);
   hi2 = (uint32_t)h0 | ((uint32_t)h1 << 16);
   lo2 = (uint32_t)l0 | ((uint32_t)l1 << 16);
+#endif
 }
 
 // 4 consecutive values -> 8-byte packed hi and lo groups
@@ -348,16 +308,6 @@ __device__ __forceinline__ void glds16(const void* gsrc_lane, void* lds_wave_bas
 #else
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc_lane,
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-#endif
-}
-
-// the same with the non-temporal cache policy (aux = 2): for streams ONE workgroup reads once
-__device__ __forceinline__ void glds16_nt(const void* gsrc_lane, void* lds_wave_base) {
-#ifdef MDM_EMU
-  emu::vm_issue(static_cast<char*>(lds_wave_base) + 16 * emu::lane_id(), gsrc_lane, 16, false);
-#else
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc_lane,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 2);
 #endif
 }
 
@@ -496,7 +446,7 @@ __device__ __forceinline__ void vmem_wait(u32x2& a, u32x2& b, u32x2& c, u32x2& d
 #endif
 
 // (float)(fp16 half HALF of `packed`) + c in ONE instruction: v_fma_mix_f32 converts its 16-bit source on the fly (h * 1.0 + c),
-// where the plain form is a v_cvt_f32_f16 and an add per element.  fp16 planes only (kSplitF16).
+// where the plain form is a v_cvt_f32_f16 and an add per element.  fp16 planes.
 template <int HALF> __device__ __forceinline__ float f16_half_plus(uint32_t packed, float c) {
 #ifdef MDM_EMU
   return (float)__builtin_bit_cast(f16x2, packed)[HALF] + c;

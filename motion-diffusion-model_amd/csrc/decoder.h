@@ -179,7 +179,7 @@ int decoder_layers_planes(mdm_model_t* m, const DecWorkspace& ws, const float* x
   // (use_small_gemm): the reference's full-length trans_dec checkpoint (README.md:254 humanml_trans_dec_512_bert-50steps: 196 frames,
   // no prefix, plain p_sample_loop) at the headline batch is the encoder's shape with a cross-attention block per layer.
   const bool small = !dec_sequence_tiles(m, nseq, S);
-  const int scols = small ? x3s_tn(shape.ncb) : 256, parts = (D + scols - 1) / scols;
+  const int scols = small ? X3S_TN : 256, parts = (D + scols - 1) / scols;
   const float inv_dim = 1.0f / (float)D;
   auto LN = [&]() { LnArgs a; a.small = small; a.shape = shape; a.stat_cols = scols; a.parts = parts; a.inv_dim = inv_dim; return a; };
   const X3Operand attp{ws.atth, ws.attl}, ffnp{ws.ffnh, ws.ffnl};
@@ -299,8 +299,8 @@ int decoder_layers_planes(mdm_model_t* m, const DecWorkspace& ws, const float* x
       if (int rc2 = rt_launch_status()) return rc2;
     } else {
     // sequence-tile route under guidance: the unconditional half (branch 1 = sequences B .. 2B-1) needs neither the q projection nor
-    // the attention -- every query's output is the sequence's one projected value row (elementwise.h uncond_xattn_rows_kernel); the
-    // cross out_proj below runs over all rows as before.  -75 us of a 1,138 us layer at B = 128 (profiles/r06h).
+    // the attention -- every query's output is the sequence's one projected value row.  -75 us of a 1,138 us layer at B = 128
+    // (profiles/r06h).
     const bool skip_uncond = !small && nbranch == 2;
     const int nseq_q = skip_uncond ? B : nseq, Mq = nseq_q * S;
     {
@@ -324,17 +324,10 @@ int decoder_layers_planes(mdm_model_t* m, const DecWorkspace& ws, const float* x
       if (int rc = launch_attention_args(pf, a, nullptr, nseq_q, D, H, ws.atth, ws.attl, s)) return rc;
       vsrc = kvt + D; vadd = row + D; vstride = (size_t)ntok * m->cfg.num_layers * 2 * D; vseq0 = hz.kv_B + hz.kv_b0;
     }
-    // ... and with it the whole block of those sequences is a row-constant: x' = norm1(y) + (Wo . v + bo).  Where the statistics
-    // partials are 256 columns wide and D / 4 threads fit a workgroup (every latent_dim the route runs), one small GEMM makes the B
-    // vectors o and uncond_xblock_rows_kernel writes the rows; the cross out_proj then covers the conditional half only.
-    const bool xblock_uncond = skip_uncond && scols == 256 && D % 256 == 0 && D <= 1024;
-    if (skip_uncond && !xblock_uncond) {
-      ProfScope ps(pf, MDM_PROF_ELEMENTWISE, 0.0, s);
-      MDM_LAUNCH(uncond_xattn_rows_kernel, dim3(B * ((S + 15) / 16)), dim3(D / 4 > 256 ? 256 : D / 4), 0, s, ws.atth, ws.attl, vsrc,
-                 vstride, vadd, S, D, B, vseq0);
-      if (int rc = rt_launch_status()) return rc;
-    }
-    if (xblock_uncond) {
+    // ... and with it the whole block of those sequences is a row-constant: x' = norm1(y) + (Wo . v + bo).  The route's statistics
+    // partials are 256 columns wide (!small) and D / 4 threads fit a workgroup (mdm_create: latent_dim 256 ... 1024), so one small GEMM
+    // makes the B vectors o and uncond_xblock_rows_kernel writes the rows; the cross out_proj then covers the conditional half only.
+    if (skip_uncond) {
       const float* o1; const float* o2 = nullptr;
       if (hoisted && hz.o_text != nullptr && hz.kv_b0 == 0 && hz.kv_B == B) {   // a window loop made the row constants once (loops.h)
         o1 = hz.o_text + (size_t)l * B * D;
@@ -359,7 +352,7 @@ int decoder_layers_planes(mdm_model_t* m, const DecWorkspace& ws, const float* x
     {
       LnArgs a = LN(); a.res = Y; a.rstat = sY; a.rgamma = m->L(l, "norm1.weight"); a.rbeta = m->L(l, "norm1.bias"); a.ostat = sX;
       if (int rc = launch_x3_ln(pf, MDM_PROF_LINEAR, 2, attp, P.out_proj2, m->L(l, "multihead_attn.out_proj.bias"), a, nullptr,
-                                Xh, Xl, nullptr, xblock_uncond ? Mq : M, D, D, S, D, 0, 1.f, s)) return rc;
+                                Xh, Xl, nullptr, Mq, D, D, S, D, 0, 1.f, s)) return rc;
     }
     }   // !fused
     // ---- Y = norm2(X) + linear2(gelu(linear1(norm2(X))))

@@ -69,7 +69,7 @@ int encoder(mdm_model* m, const Workspace& ws, int nseq, int B, int S, const int
     // columns); else gemm_x3.h's sequence-sized tiles (per 256)
     const bool small = use_small_gemm(m, nseq, S);
     const X3sShape shape = x3s_shape(m->x3s, nseq);
-    const int scols = small ? x3s_tn(shape.ncb) : 256;
+    const int scols = small ? X3S_TN : 256;
     const int parts = (D + scols - 1) / scols;
     const float inv_dim = 1.0f / (float)D;
     auto LN = [&]() { LnArgs a; a.small = small; a.shape = shape; a.stat_cols = scols; a.parts = parts; a.inv_dim = inv_dim; return a; };
@@ -168,7 +168,7 @@ int outproj_x3(mdm_model* m, const Workspace& ws, int nseq, int B, int T, const 
     LnArgs a; a.astat = ws.stat2; a.colsum = m->c_out; a.inv_dim = 1.0f / (float)D;
     a.small = use_small_gemm(m, nseq, S);            // (the same decision the encoder took: who wrote stat2)
     a.shape = x3s_shape(m->x3s, nseq);
-    a.stat_cols = a.small ? x3s_tn(a.shape.ncb) : 256;
+    a.stat_cols = a.small ? X3S_TN : 256;
     a.parts = (D + a.stat_cols - 1) / a.stat_cols;
     if (int rc = launch_x3_ln(nullptr, MDM_PROF_OUTPROJ, 4, X3Operand{ws.tokh, ws.tokl}, m->out_planes_f, m->b_out, a,
                               out_tok, nullptr, nullptr, nullptr, nseq * S, ldo, D, S, D, 0, 1.f, s)) return rc;

@@ -1,5 +1,5 @@
 // Split-precision ("f16x3"; round 1: "bf16x3") MFMA GEMM for the encoder's dense contractions:
-//     C[m][n] = sum_k A[m][k] * W[n][k],   A = Ah + Al,  W = Wh + Wl  (16-bit planes: fp16 by default, common.h kSplitF16 / split_p16)
+//     C[m][n] = sum_k A[m][k] * W[n][k],   A = Ah + Al,  W = Wh + Wl  (fp16 planes: common.h split_p16)
 //             ~ sum_k  Ah*Wh + Ah*Wl + Al*Wh            three fp16 MFMA passes, fp32 accumulate.
 //
 // Why: the reference computes these `addmm`s in fp32 (model/mdm.py:77-84 -> torch TransformerEncoderLayer) and
@@ -244,7 +244,7 @@ enum : unsigned {
   X3_PAIR = 1u << 9,         // one tile serves both guidance branches of a sample
 };
 // FOLD / OSTAT / RES == 3: LayerNorm folded into the GEMMs (X3Epilogue).
-// T16: the tile is 208 rows -- six 32-row sub-tiles plus ONE 16-row sub-tile (rows 192-207) on v_mfma_f32_16x16x32_bf16 --
+// T16: the tile is 208 rows -- six 32-row sub-tiles plus ONE 16-row sub-tile (rows 192-207) on v_mfma_f32_16x16x32_f16 --
 // for row extents <= 208 (S = 197: 11 pad rows instead of 27, i.e. 6.5 of 7 units of matrix work and 13 of 14 A groups).
 // The 16-row sub-tile needs the wave's W fragments in the 16x16x32 operand layout; they are derived from the 32x32x16
 // fragments in registers by two lane swaps per dword (common.h frag32_to_frag16), not fetched a second time.
@@ -1067,7 +1067,7 @@ __global__ __launch_bounds__(64 * X3_NWAVE, 2) void gemm_x3_kernel(X3Operand A, 
         if constexpr (RES == 1) {
           const f32x4 q4 = rr[t % RR][g];
           v4.x += q4[0]; v4.y += q4[1]; v4.z += q4[2]; v4.w += q4[3];
-        } else if constexpr (RES_PLANES && kSplitF16) {
+        } else if constexpr (RES_PLANES) {
           // x = hi + lo (RES == 3: minus the row mean, times rstd * gamma; beta rides in the bias vector bb4): the planes are
           // converted inside the adds (common.h f16_half_plus), the mean leaves before anything is scaled
           const u32x2 a = rh[t % RR][g], b = rl[t % RR][g];
@@ -1082,18 +1082,6 @@ __global__ __launch_bounds__(64 * X3_NWAVE, 2) void gemm_x3_kernel(X3Operand A, 
           } else {
             v4.x += d0; v4.y += d1; v4.z += d2; v4.w += d3;
           }
-        } else if constexpr (RES_PLANES) {
-          const u32x2 a = rh[t % RR][g], b = rl[t % RR][g];
-          float4 x4 = make_float4(
-              p16_to_f32((p16_t)(a[0] & 0xffffu)) + p16_to_f32((p16_t)(b[0] & 0xffffu)),
-              p16_to_f32((p16_t)(a[0] >> 16)) + p16_to_f32((p16_t)(b[0] >> 16)),
-              p16_to_f32((p16_t)(a[1] & 0xffffu)) + p16_to_f32((p16_t)(b[1] & 0xffffu)),
-              p16_to_f32((p16_t)(a[1] >> 16)) + p16_to_f32((p16_t)(b[1] >> 16)));
-          if constexpr (RES == 3) {   // the residual is LayerNorm(x), rebuilt from x's planes and its row statistics
-            x4.x = (x4.x - st.x) * st.y * g4.x; x4.y = (x4.y - st.x) * st.y * g4.y;   // (+ beta: in bb4)
-            x4.z = (x4.z - st.x) * st.y * g4.z; x4.w = (x4.w - st.x) * st.y * g4.w;
-          }
-          v4.x += x4.x; v4.y += x4.y; v4.z += x4.z; v4.w += x4.w;
         }
         if constexpr (OSTAT) {   // partial (sum, centred sum of squares) of this row over the wave's 32 columns
           const float s1 = sum_lanes8((v4.x + v4.y) + (v4.z + v4.w));

@@ -65,13 +65,7 @@ const char* mdm_build_info(void) {
 #else
          "0"
 #endif
-         ";planes="
-#ifdef MDM_SPLIT_BF16
-         "bf16"
-#else
-         "f16"
-#endif
-      ;
+         ";planes=f16";
 }
 const char* mdm_last_error(void) { return g_err.c_str(); }
 
@@ -131,11 +125,6 @@ int mdm_create(const mdm_config_t* cfg, mdm_model_t** out) {
   e["output_process.poseFinal.weight"] = jf * d;
   e["output_process.poseFinal.bias"] = jf;
   e["sequence_pos_encoder.pe"] = (int64_t)cfg->max_len * d;
-#ifdef MDM_PROBES   // the probe library's whole-bench A/B scripts (tools/) preset a handle's options from the environment, once, here
-  if (const char* e = getenv("MDM_X3S_MAX_SEQS")) m->x3s.max_seqs = atoi(e);
-  if (const char* e = getenv("MDM_X3S_RT")) m->x3s.row_tiles = atoi(e);
-  if (const char* e = getenv("MDM_X3S_NCB")) m->x3s.ncb = atoi(e);
-#endif
   *out = m;
   return MDM_OK;
 }
@@ -412,9 +401,6 @@ int mdm_prepare(mdm_model_t* m, void* const_ws, size_t const_ws_bytes, void* str
       if (int rc = launch_pack_weights(scratch_w, hi, hi + n, D, m->jf_k, s, m->range_flag)) return rc;
     }
     m->lnfold = true;
-#ifdef MDM_PROBES   // A/B switch of the probe library: MDM_LNFOLD=0 runs the LayerNorms as kernels on the planes again
-    if (const char* e = getenv("MDM_LNFOLD")) m->lnfold = e[0] != '0';
-#endif
   }
   m->prepared = true;
   return MDM_OK;
@@ -557,12 +543,13 @@ int mdm_randn(float* out, const float* init, const float* eps, float a, float s,
 
 #ifdef MDM_PROBES
 int mdm_debug_set(int what, int value) {
-  // 0 (GEMM ablations), 2 (4-wave workgroups), 6 (sync / pipe probe), 8 (start delay): experiments of gemm_x3.h that were removed
-  // with their code (lab/README.md) -- refused, so that an old A/B script does not measure the product against itself
-  if (what == 0 || what == 2 || what == 6 || what == 8)
-    return fail(MDM_EINVAL, "mdm_debug_set: code " + std::to_string(what) + " belonged to a gemm_x3.h experiment that has been removed");
+  // 0 (GEMM ablations), 2 (4-wave workgroups), 6 (sync / pipe probe), 8 (start delay) of gemm_x3.h and 3 (ablations of
+  // attention_x3.h): experiments that were removed with their code (lab/README.md) -- refused, so that an old A/B script does not
+  // measure the product against itself
+  if (what == 0 || what == 2 || what == 3 || what == 6 || what == 8)
+    return fail(MDM_EINVAL, "mdm_debug_set: code " + std::to_string(what) + " belonged to a " +
+                                (what == 3 ? "attention_x3.h" : "gemm_x3.h") + " experiment that has been removed");
   if (what == 1) g_x3_reuse_planes = value;
-  if (what == 3) g_ax_ablate = value;
   if (what == 4) g_f6_reference = value;
   if (what == 5) g_f6_linear = value;
 #ifndef MDM_EMU

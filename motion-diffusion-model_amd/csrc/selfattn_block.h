@@ -441,7 +441,7 @@ __global__ __launch_bounds__(64 * SB_WAVES, 1) void selfattn_block_kernel(SelfAt
       mx = fmaxf(mx, fmaxf(fmaxf(s0, s1), fmaxf(s2, s3)));
     }
   mx = fmaxf(mx, shfl_xor_f32(mx, 32));
-  if constexpr (kSplitF16) mx -= 6.931471805599453f;      // probabilities as hi / lo of p * 2^10: cancels in 1 / sum
+  mx -= 6.931471805599453f;      // probabilities as hi / lo of p * 2^10: cancels in 1 / sum
   float sum = 0.f;
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)

@@ -307,7 +307,7 @@ __global__ __launch_bounds__(64 * XB_WAVES, 1) void xattn_block_kernel(XattnArgs
         mx = fmaxf(mx, s);
       }
     mx = fmaxf(mx, shfl_xor_f32(mx, 32));
-    if constexpr (kSplitF16) mx -= 6.931471805599453f;    // probabilities as hi / lo of p * 2^10 (attention_x3.h): cancels in 1 / sum
+    mx -= 6.931471805599453f;    // probabilities as hi / lo of p * 2^10 (attention_x3.h): cancels in 1 / sum
     float sum = 0.f;
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)

@@ -7,8 +7,8 @@
 //   * MFMA lane<->element maps    -> exactly the gfx950 layouts (cdna_hip_programming.md section 3):
 //       v_mfma_f32_32x32x2_f32 : A[i=l&31][k=l>>5], B[k=l>>5][j=l&31],
 //                                D[reg]: col=l&31, row=(reg&3)+8*(reg>>2)+4*(l>>5); k-ordered fmaf chain
-//       v_mfma_f32_32x32x16_bf16: A/B 8 bf16 per lane, k = 8*(l>>5)+e ; same D layout, fp32 accumulate
-//       v_mfma_f32_16x16x32_bf16, v_permlane32_swap / v_permlane16_swap (the GEMM's 16-row last sub-tile)
+//       v_mfma_f32_32x32x16_f16: A/B 8 fp16 per lane, k = 8*(l>>5)+e ; same D layout, fp32 accumulate
+//       v_mfma_f32_16x16x32_f16, v_permlane32_swap / v_permlane16_swap (the GEMM's 16-row last sub-tile)
 // It validates index math / masking / epilogues, NOT timing, and is never part of the product path.
 #pragma once
 #include <ucontext.h>
@@ -164,33 +164,7 @@ inline f32x16 mfma_f32_32x32x2(float a, float b, f32x16 c) {
   return c;
 }
 
-inline float bf16_to_f32(short s) {
-  uint32_t u = ((uint32_t)(uint16_t)s) << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
-inline f32x16 mfma_f32_32x32x16_bf16(p16x8 a, p16x8 b, f32x16 c) {
-  WaveBuf& w = blk().waves[wave_id()];
-  int l = lane_id();
-  w.ha[l] = a;
-  w.hb[l] = b;
-  wave_barrier();
-  int j = l & 31, h = l >> 5;
-  for (int r = 0; r < 16; ++r) {
-    int i = (r & 3) + 8 * (r >> 2) + 4 * h;
-    float acc = c[r];
-    for (int g = 0; g < 2; ++g)
-      for (int e = 0; e < 8; ++e)
-        acc = fmaf(bf16_to_f32(w.ha[i + 32 * g][e]), bf16_to_f32(w.hb[j + 32 * g][e]), acc);
-    c[r] = acc;
-  }
-  wave_barrier();
-  return c;
-}
-
-// v_mfma_f32_32x32x16_f16: the bf16 form's layout with fp16 elements
+// v_mfma_f32_32x32x16_f16: A/B 8 fp16 per lane, k = 8*(l>>5)+e; D layout of the fp32 form above, fp32 accumulate
 inline f32x16 mfma_f32_32x32x16_f16(f16x8 a, f16x8 b, f32x16 c) {
   WaveBuf& w = blk().waves[wave_id()];
   int l = lane_id();
@@ -248,27 +222,7 @@ inline f32x16 mfma_scale_f32_32x32x64_fp6(i32x8 a, i32x8 b, f32x16 c, int scale_
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-// v_mfma_f32_16x16x32_bf16: A row / B column = l&15, k = 8*(l>>4)+e; D[reg]: row 4*(l>>4)+reg, column l&15
-inline f32x4 mfma_f32_16x16x32_bf16(p16x8 a, p16x8 b, f32x4 c) {
-  WaveBuf& w = blk().waves[wave_id()];
-  int l = lane_id();
-  w.ha[l] = a;
-  w.hb[l] = b;
-  wave_barrier();
-  int j = l & 15, g = l >> 4;
-  for (int r = 0; r < 4; ++r) {
-    int i = 4 * g + r;
-    float acc = c[r];
-    for (int kg = 0; kg < 4; ++kg)
-      for (int e = 0; e < 8; ++e)
-        acc = fmaf(bf16_to_f32(w.ha[i + 16 * kg][e]), bf16_to_f32(w.hb[j + 16 * kg][e]), acc);
-    c[r] = acc;
-  }
-  wave_barrier();
-  return c;
-}
-
-// v_mfma_f32_16x16x32_f16: the bf16 form's layout with fp16 elements
+// v_mfma_f32_16x16x32_f16: A row / B column = l&15, k = 8*(l>>4)+e; D[reg]: row 4*(l>>4)+reg, column l&15
 inline f32x4 mfma_f32_16x16x32_f16(f16x8 a, f16x8 b, f32x4 c) {
   WaveBuf& w = blk().waves[wave_id()];
   int l = lane_id();

@@ -46,8 +46,9 @@ def test_probe_surface_is_not_in_the_production_library(lib):
         assert not hasattr(lib.lib, n), f"{n} leaked into the production library"
         assert hasattr(probe.lib, n)
     assert not lib.has_probes and probe.has_probes
-    # switches of gemm_x3.h experiments that were removed with their code are refused, not silently ignored; a live one is accepted
-    for code in (0, 2, 6, 8):
+    # switches of gemm_x3.h / attention_x3.h experiments that were removed with their code are refused, not silently ignored; a live
+    # one is accepted
+    for code in (0, 2, 3, 6, 8):
         assert probe.lib.mdm_debug_set(code, 0) == -1 and b"removed" in probe.lib.mdm_last_error(), code
     assert probe.lib.mdm_debug_set(1, 0) == 0
 

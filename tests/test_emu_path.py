@@ -577,9 +577,8 @@ def test_engine_options_are_set_through_the_abi_not_the_environment(lib, monkeyp
                mask_frames=1, arch=0, context_len=0)
     monkeypatch.setenv("MDM_X3S_MAX_SEQS", "0")
     monkeypatch.setenv("MDM_X3S_RT", "2")
-    if not lib.has_probes:      # (the probe / emulator builds preset new handles from these two variables for tools/' A/B scripts)
-        e = Engine(cfg, lib=lib)
-        assert e.get_option("small_gemm_max_seqs") == 80 and e.get_option("small_gemm_row_tiles") == 0
+    e = Engine(cfg, lib=lib)        # (on every build: the probe / emulator builds read these two variables until round 13)
+    assert e.get_option("small_gemm_max_seqs") == 80 and e.get_option("small_gemm_row_tiles") == 0
     monkeypatch.delenv("MDM_X3S_MAX_SEQS")
     monkeypatch.delenv("MDM_X3S_RT")
     e = Engine(cfg, lib=lib, options={"small_gemm_row_tiles": 2})

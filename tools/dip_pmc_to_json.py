@@ -24,15 +24,15 @@ def classify(name):
             return k
     if "gemm_x3s_kernel" in name or "true, " in name or "false, " in name:
         args = [a.strip() for a in name[name.rfind("<") + 1:name.rfind(">")].split(",")] if "<" in name else []
-        if len(args) >= 12:      # <RT, NCB, NSUB, MULTI, ACT, RES, OUT_F32, OUT_PLANES, OUT_QKV, FOLD, OSTAT, EMBED>
-            act, res, f32, planes, qkv, fold, ostat = args[4], args[5], args[6], args[7], args[8], args[9], args[10]
-            if qkv == "true":
+        if len(args) == 6:       # <RT, NSUB, MULTI, ACT, RES, FLAGS>, FLAGS = the X3_* bits of csrc/gemm_x3.h
+            act, res, flags = args[3], args[4], int(args[5].rstrip("u"))
+            if flags & 4:        # X3_OUT_QKV
                 return "gemm_x3s in_proj"
-            if ostat == "true":
+            if flags & 16:       # X3_OSTAT
                 return "gemm_x3s out_proj|cross out_proj|linear2" if res == "3" else "gemm_x3s out_proj layer0"
             if act == "1":
                 return "gemm_x3s linear1"
-            if f32 == "true":
+            if flags & 1:        # X3_OUT_F32
                 return "gemm_x3s q-projection|OutputProcess"
         return "gemm_x3s other"
     return None
