@@ -105,7 +105,11 @@ void mdm_destroy(mdm_model_t* m);
  *                                 32 / 64-row tiles of the latency regime (csrc/gemm_x3s.h) instead of the sequence-sized tiles
  *                                 (csrc/gemm_x3.h).  Default 80 (the measured cross-over, profiles/r05k_crossovers.md).  0: never -- which also sends the
  *                                 trans_dec (DiP) decoder to its fp32-skeleton route (csrc/gemm_f32.h).  The parity tests use it
- *                                 to hold every route against the reference's fixtures.
+ *                                 to hold every route against the reference's fixtures.  A trans_dec forward of MORE sequences than
+ *                                 this leaves the row tiles only where its sequences are 129 .. 224 tokens long: there it runs on
+ *                                 the sequence tiles with in_proj + attention and the three-launch cross-attention (the fused forms
+ *                                 below belong to the row tiles), and under guidance computes layer 0's self-attention block once
+ *                                 and the unconditional half's cross-attention as row constants.
  *   MDM_OPT_SMALL_GEMM_ROW_TILES  0 (default): 32-row tiles up to 12 sequences, 64-row tiles above; 1 / 2: pin 32 / 64 rows.
  *   MDM_OPT_DEC_FUSED_XATTN       the cross-attention block of a trans_dec layer on the operand-plane route -- query projection with
  *                                 norm1 folded, attention over the text memory, out_proj + residual + row statistics (model/mdm.py:
@@ -321,6 +325,7 @@ int mdm_sample_loop_dec(mdm_model_t* m, const mdm_sample_dec_params_t* p, float*
  * bracketed by a hipEvent pair on the launch stream and bucketed by kernel class; mdm_profile_read waits for
  * the events of one class and returns their summed duration, the launch count and the ALGORITHMIC flops of
  * those launches (2MNK per GEMM, 4 S^2 hd per (sequence, head) of attention; 0 for the HBM-bound classes).
+ * (The CPU emulation of the test suite has no events: it reports the launch counts, with times and flops 0.)
  * The event records perturb the stream slightly, so throughput is always timed with profiling off. */
 #define MDM_PROF_LINEAR 0       /* encoder GEMMs: in_proj, out_proj, linear1, linear2 */
 #define MDM_PROF_ATTENTION 1

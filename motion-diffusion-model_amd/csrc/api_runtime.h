@@ -56,7 +56,9 @@ inline int lds_fail(int rc, const char* what) {
 // Opt-in per-launch timing (mdm_profile_enable): one hipEvent pair per kernel launch, bucketed by kernel class.
 struct Profiler {
   bool on = false;
-#ifndef MDM_EMU
+#ifdef MDM_EMU
+  int64_t launches[MDM_PROF_NUM] = {};   // the CPU emulation has no events: it counts the scopes per class (times and flops read 0)
+#else
   struct Rec { int cat; hipEvent_t a, b; double flops; };
   std::vector<Rec> recs;
   std::vector<hipEvent_t> pool;
@@ -85,7 +87,7 @@ struct ProfScope {   // records start on construction, stop on destruction (both
   }
   ~ProfScope() { if (p) (void)hipEventRecord(p->recs[idx].b, s); }
 #else
-  ProfScope(Profiler*, int, double, hipStream_t) {}
+  ProfScope(Profiler* prof, int cat, double, hipStream_t) { if (prof && prof->on) ++prof->launches[cat]; }
 #endif
 };
 

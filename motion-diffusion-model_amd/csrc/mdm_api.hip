@@ -616,6 +616,8 @@ int mdm_profile_read(mdm_model_t* m, int32_t category, double* total_ms, int64_t
     if (hipEventElapsedTime(&dt, r.a, r.b) != hipSuccess) return fail(MDM_EHIP, "mdm_profile_read: hipEventElapsedTime failed");
     ms += dt; fl += r.flops; ++n;
   }
+#else
+  n = m->prof.launches[category];
 #endif
   if (total_ms) *total_ms = ms;
   if (launches) *launches = n;
@@ -628,6 +630,8 @@ int mdm_profile_reset(mdm_model_t* m) {
 #ifndef MDM_EMU
   for (auto& r : m->prof.recs) { m->prof.pool.push_back(r.a); m->prof.pool.push_back(r.b); }
   m->prof.recs.clear();
+#else
+  for (auto& c : m->prof.launches) c = 0;
 #endif
   return MDM_OK;
 }

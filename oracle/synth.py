@@ -155,6 +155,58 @@ def synth_dip_y(B, pred_len, context_len, seed, text_lengths, scale=7.5, lengths
             "scale": torch.ones(B) * scale}
 
 
+def synth_dip_state_dict_hostile(seed=0, latent_dim=512, ff_size=1024, num_layers=8, input_feats=263, bert_dim=768):
+    """The recipe of `synth_state_dict_hostile` on the keys of `synth_dip_state_dict` (same keys / shapes, deterministic in `seed`):
+    log-normal gamma over [0.05, 8] with six channels pinned to each end in norm1 .. norm3; the model-wide outlier channels in the
+    three betas and in the biases that feed the residual stream (both attentions' out_proj, linear2, poseEmbedding), four outlier
+    features in linear1's bias; three ten-fold rows in every weight matrix (both in_proj / out_proj pairs, linear1 / 2,
+    poseEmbedding, embed_text, poseFinal); the text embedding is scaled 20x by `synth_dip_y_hostile`.  The largest gamma-folded weight
+    is 8 * 10 * sqrt(6 / (4 d)) < 7 at d >= 256: far inside the f16x3 weight planes (|w| < 255.9, mdm_weights_in_range)."""
+    sd = synth_dip_state_dict(seed, latent_dim, ff_size, num_layers, input_feats, bert_dim)
+    g = torch.Generator().manual_seed(seed + 7919)
+    d = latent_dim
+    out_ch = torch.randperm(d, generator=g)[:4]
+
+    def rows10(w, n=3):
+        idx = torch.randperm(w.shape[0], generator=g)[:n]
+        w[idx] *= 10.0
+
+    def outlier_vec(v, idx, lo=50.0, hi=300.0):
+        typ = v.abs().mean().clamp_min(1e-3)
+        mag = lo + (hi - lo) * torch.rand(len(idx), generator=g)
+        sign = torch.where(torch.rand(len(idx), generator=g) < 0.5, -1.0, 1.0)
+        v[idx] = sign * mag * typ
+
+    for i in range(num_layers):
+        p = f"seqTransDecoder.layers.{i}."
+        for n in ("norm1", "norm2", "norm3"):
+            gam = torch.exp(0.7 * torch.randn(d, generator=g)).clamp(0.05, 8.0)
+            ends = torch.randperm(d, generator=g)[:12]
+            gam[ends[:6]] = 8.0
+            gam[ends[6:]] = 0.05
+            sd[p + n + ".weight"] = gam
+            outlier_vec(sd[p + n + ".bias"], out_ch)
+        for n in ("self_attn.in_proj_weight", "self_attn.out_proj.weight", "multihead_attn.in_proj_weight",
+                  "multihead_attn.out_proj.weight", "linear1.weight", "linear2.weight"):
+            rows10(sd[p + n])
+        for n in ("self_attn.out_proj.bias", "multihead_attn.out_proj.bias", "linear2.bias"):
+            outlier_vec(sd[p + n], out_ch)
+        outlier_vec(sd[p + "linear1.bias"], torch.randperm(ff_size, generator=g)[:4])
+    rows10(sd["input_process.poseEmbedding.weight"])
+    outlier_vec(sd["input_process.poseEmbedding.bias"], out_ch)
+    rows10(sd["embed_text.weight"])
+    rows10(sd["output_process.poseFinal.weight"])
+    return sd
+
+
+def synth_dip_y_hostile(B, pred_len, context_len, seed, text_lengths, scale=7.5, lengths=None, bert_dim=768, njoints=263):
+    """`synth_dip_y` with the cached token embeddings scaled 20x (encoder features are not unit-variance)."""
+    y = synth_dip_y(B, pred_len, context_len, seed, text_lengths, scale, lengths, bert_dim, njoints)
+    enc, pad = y["text_embed"]
+    y["text_embed"] = (enc * 20.0, pad)
+    return y
+
+
 def synth_bert(texts, bert_dim=768, junk=5.0):
     """Functional stand-in for model/BERT/BERT_encoder.py:26-32 `BERT.forward(texts)`: -> (last_hidden_state [len(texts), Ntok, 768],
     attention_mask bool [len(texts), Ntok]).  A prompt maps to a block of (words + 2) token rows -- [CLS] w1 .. wn [SEP], as the
