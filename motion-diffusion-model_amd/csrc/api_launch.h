@@ -15,6 +15,16 @@ struct Workspace {
   size_t bytes;
 };
 
+// The six operand planes of attention_x3.h over a qkv region of nseq * SP * 3 D floats (SP: S rounded up to whole 32-key tiles)
+QkvPlanes carve_qkv_planes(float* qkv, size_t nseq, size_t S, size_t D, int H) {
+  const size_t NKT = (S + 31) / 32, SP = 32 * NKT, plane = nseq * SP * D;
+  p16_t* q = reinterpret_cast<p16_t*>(qkv);
+  QkvPlanes qp{};
+  qp.qh = q; qp.SP = (int)SP; qp.NKT = (int)NKT; qp.H = H;
+  if (q != nullptr) { qp.ql = q + plane; qp.kh = q + 2 * plane; qp.kl = q + 3 * plane; qp.vh = q + 4 * plane; qp.vl = q + 5 * plane; }
+  return qp;
+}
+
 Workspace carve(const mdm_model* m, int nseq, int T, void* base) {
   const size_t D = m->cfg.latent_dim, FF = m->cfg.ff_size, S = (size_t)T + 1, M = (size_t)nseq * S;
   size_t off = 0;
@@ -44,12 +54,7 @@ Workspace carve(const mdm_model* m, int nseq, int T, void* base) {
   const size_t parts = (D + 127) / 128;   // per-row partial statistics: per 256 columns (gemm_x3.h) or per 128 (gemm_x3s.h)
   w.stat1 = take(M * parts * 2 + 4);   // (+ 16 bytes: gemm_x3.h stats_dma's last unit of a tile that starts 8-byte aligned)
   w.stat2 = take(M * parts * 2 + 4);
-  {
-    const size_t plane = (size_t)nseq * SP * D;
-    p16_t* q = reinterpret_cast<p16_t*>(w.qkv);
-    w.qp = QkvPlanes{q, q ? q + plane : nullptr, q ? q + 2 * plane : nullptr, q ? q + 3 * plane : nullptr,
-                     q ? q + 4 * plane : nullptr, q ? q + 5 * plane : nullptr, (int)SP, (int)NKT, m->cfg.num_heads};
-  }
+  w.qp = carve_qkv_planes(w.qkv, nseq, S, D, m->cfg.num_heads);
   w.bytes = off;
   return w;
 }
@@ -156,6 +161,37 @@ int launch_attention_x3(Profiler* pf, const QkvPlanes& qp, const int* lengths, i
   return launch_attention_x3_nkt<false>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
 }
 
+// One split-precision GEMM as its caller describes it (gemm_x3.h X3Kind names the epilogue of the folded-LayerNorm stacks).  The
+// encoder's and the decoder's LN() set what is constant over a stack; a call site names what differs.
+struct X3Call {
+  X3Kind kind = X3K_OUT_LN_RES;
+  Profiler* pf = nullptr; int prof_cat = MDM_PROF_LINEAR;
+  X3Operand a{nullptr, nullptr}; X3Weights w{nullptr, nullptr}; const float* bias = nullptr;
+  float* out = nullptr; p16_t* oh = nullptr; p16_t* ol = nullptr; const QkvPlanes* qp = nullptr;   // fp32 rows / planes / Q, K, V^T planes
+  int M = 0, N = 0, K = 0, S = 0, D = 0;
+  int scale_cols = 0; float col_scale = 1.f;
+  const float* astat = nullptr; const float* colsum = nullptr;                                   // FOLD
+  X3Operand res{nullptr, nullptr}; const float* rstat = nullptr; const float* rgamma = nullptr; const float* rbeta = nullptr;  // residual
+  float* ostat = nullptr;                                                                       // OSTAT
+  int parts = 1; float inv_dim = 1.f;
+  const float* res_f32 = nullptr; int emb_T = 1, emb_B = 1, emb_nbranch = 1;                     // fp32 residual; EMBED (X3K_EMBED)
+  bool small = false;      // the small-row-count kernel (gemm_x3s.h): the whole forward runs on one of the two kernels
+  X3sShape shape{1};       // ... and on ONE tile shape of it (x3s_shape(m->x3s, nseq))
+  int stat_cols = 256;     // columns per partial of astat / rstat (what the PRODUCER's kernel wrote)
+};
+// The one place an X3Epilogue (a kernel argument, gemm_x3.h) is filled
+X3Epilogue x3_epilogue(const X3Call& c) {
+  X3Epilogue ep{};
+  ep.out = c.out; ep.bias = c.bias; ep.res = c.res_f32; ep.resh = c.res.hi; ep.resl = c.res.lo; ep.oh = c.oh; ep.ol = c.ol;
+  ep.ld = c.N; ep.scale_cols = c.scale_cols; ep.col_scale = c.col_scale;
+  if (c.qp != nullptr) ep.qkv = *c.qp;
+  ep.S = c.S; ep.D = c.D;
+  ep.astat = c.astat; ep.colsum = c.colsum; ep.rstat = c.rstat; ep.rgamma = c.rgamma; ep.rbeta = c.rbeta; ep.ostat = c.ostat;
+  ep.stat_parts = c.parts; ep.inv_dim = c.inv_dim; ep.emb_T = c.emb_T; ep.emb_B = c.emb_B; ep.emb_nbranch = c.emb_nbranch;
+  ep.stat_cols = c.stat_cols;
+  return ep;
+}
+
 #ifdef MDM_PROBES
 // TEST-ONLY mode (mdm_debug_set(5, 1)): the `f32` mode's encoder GEMMs on the f16f6 kernel, UNFUSED -- operands packed per
 // call into a library-owned scratch (the one exception to "the caller owns every buffer": a debug path) -- so that the
@@ -189,8 +225,9 @@ int launch_linear_f6_debug(Profiler* pf, const float* in, int ld_in, const float
   const int npad = (N + 31) / 32 * 32;
   MDM_LAUNCH(pack_weight_f16f6_kernel, dim3((npad * (K / 32) + 255) / 256), dim3(256), 0, s, w, wfh, wfl, N, K);
   if (int rc = rt_launch_status()) return rc;
-  X3Epilogue ep{out, bias, res, nullptr, nullptr, nullptr, nullptr, N, scale_cols, col_scale, QkvPlanes{}, 0, 0,
-                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1.f, 1, 1, 1, 1.f};
+  X3Call c; c.out = out; c.bias = bias; c.res_f32 = res; c.N = N; c.scale_cols = scale_cols; c.col_scale = col_scale;
+  X3Epilogue ep = x3_epilogue(c);
+  ep.acc_scale = 1.f;   // (pack_weight_f16f6_kernel's planes are unscaled: no 2^8 to undo)
   const X3Operand a{reinterpret_cast<const p16_t*>(pa.h16), reinterpret_cast<const p16_t*>(pa.rec)};
   const int rc = launch_gemm_f16f6(a, X3Weights{wfh, wfl}, ep, M, N, K, act, s);
   if (rc != 0) return fail(MDM_EUNSUPPORTED, "f16f6 debug mode: launch failed");
@@ -244,9 +281,9 @@ int launch_linear_x3(Profiler* pf, X3Operand a, X3Weights w, const float* bias, 
   if (K % X3_BK != 0) return fail(MDM_EINVAL, "f16x3 linear: K must be a multiple of 32");
   if (N % 4 != 0) return fail(MDM_EINVAL, "f16x3 linear: N must be a multiple of 4");
   ProfScope ps(pf, MDM_PROF_LINEAR, 2.0 * M * (double)N * K, s);
-  X3Epilogue ep{out, bias, res, res_planes.hi, res_planes.lo, oh, ol, N, scale_cols, col_scale, QkvPlanes{}, 0, 0,
-                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1.f, 1, 1, 1};
-  const int rc = launch_gemm_x3(a, w, ep, M, N, K, act, seq_len, s);
+  X3Call c; c.out = out; c.oh = oh; c.ol = ol; c.bias = bias; c.res_f32 = res; c.res = res_planes; c.N = N;
+  c.scale_cols = scale_cols; c.col_scale = col_scale;
+  const int rc = launch_gemm_x3(a, w, x3_epilogue(c), M, N, K, act, seq_len, s);
   if (rc == -2) return fail(MDM_EUNSUPPORTED, "f16x3 linear: unsupported (activation, residual, output) combination");
   return rt_launch_status();
 }
@@ -259,25 +296,13 @@ int launch_in_proj_x3(Profiler* pf, X3Operand a, X3Weights w, const float* bias,
   if (D % X3_BK != 0) return fail(MDM_EINVAL, "f16x3 in_proj: latent_dim must be a multiple of 32");
   const double rows = pair_B > 0 ? (double)pair_B * (S + 1) : (double)nseq * S;     // the rows actually computed
   ProfScope ps(pf, MDM_PROF_LINEAR, 2.0 * rows * 3.0 * D * (double)D, s);
-  X3Epilogue ep{nullptr, bias, nullptr, nullptr, nullptr, nullptr, nullptr, 3 * D, D, qscale, qp, S, D,
-                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1.f, 1, 1, 1};
-  const int rc = launch_gemm_x3_qkv(a, w, ep, nseq, S, D, s, pair_B);
+  X3Call c; c.bias = bias; c.qp = &qp; c.N = 3 * D; c.S = S; c.D = D; c.scale_cols = D; c.col_scale = qscale;
+  const int rc = launch_gemm_x3_qkv(a, w, x3_epilogue(c), nseq, S, D, s, pair_B);
   if (rc == -2) return fail(MDM_EUNSUPPORTED, pair_B > 0 ? "f16x3 in_proj: the paired layer-0 launch does not cover this shape"
                                                          : "f16x3 in_proj: sequences longer than 224 tokens");
   return rt_launch_status();
 }
 
-// One GEMM of the folded-LayerNorm encoder (gemm_x3.h launch_gemm_x3_ln kinds)
-struct LnArgs {
-  const float* astat = nullptr; const float* colsum = nullptr;                                   // FOLD
-  X3Operand res{nullptr, nullptr}; const float* rstat = nullptr; const float* rgamma = nullptr; const float* rbeta = nullptr;  // residual
-  float* ostat = nullptr;                                                                       // OSTAT
-  int parts = 1; float inv_dim = 1.f;
-  const float* res_f32 = nullptr; int emb_T = 1, emb_B = 1, emb_nbranch = 1;                     // EMBED (kind 5)
-  bool small = false;      // the small-row-count kernel (gemm_x3s.h): the whole forward runs on one of the two kernels
-  X3sShape shape{1};       // ... and on ONE tile shape of it (x3s_shape(m->x3s, nseq))
-  int stat_cols = 256;     // columns per partial of astat / rstat (what the PRODUCER's kernel wrote)
-};
 // The latency regime (gemm_x3s.h): a forward of at most MDM_OPT_SMALL_GEMM_MAX_SEQS sequences runs its GEMMs on 32 / 64-row tiles --
 // and so does EVERY forward whose sequences are longer than gemm_x3.h's 224-row sequence tile (round 6: the row tiles do not care how
 // long a sequence is; attention_long.h takes the attention)
@@ -285,34 +310,32 @@ inline bool use_small_gemm(const mdm_model* m, int nseq, int S) {
   return m->precision == MDM_PREC_F16X3 && m->lnfold && (nseq <= m->x3s.max_seqs || S > X3_TM) &&
          m->cfg.latent_dim % 128 == 0 && m->cfg.latent_dim % 256 == 0 && m->cfg.ff_size % 256 == 0;
 }
-int launch_x3_ln(Profiler* pf, int prof_cat, int kind, X3Operand a, X3Weights w, const float* bias, const LnArgs& ln,
-                 float* out, p16_t* oh, p16_t* ol, const QkvPlanes* qp, int M, int N, int K, int S, int D,
-                 int scale_cols, float col_scale, hipStream_t s) {
+int launch_x3_ln(const X3Call& c, hipStream_t s) {
+  const X3Kind kind = c.kind;
+  const int M = c.M, N = c.N, K = c.K, S = c.S;
   if (K % X3_BK != 0 || N % 4 != 0) return fail(MDM_EINVAL, "f16x3 linear: K % 32 and N % 4 must be 0");
   // partial statistics per row: D / 256 on gemm_x3.h's tiles (<= 4), D / 128 on gemm_x3s.h's (<= 8); D <= 1024 (mdm_create)
-  if (ln.parts < 1 || ln.parts > (ln.small ? 8 : 4)) return fail(MDM_EUNSUPPORTED, "folded LayerNorm: too many partial sums per row (D <= 1024)");
-  ProfScope ps(pf, prof_cat, 2.0 * M * (double)N * K, s);
-  X3Epilogue ep{out, bias, ln.res_f32, ln.res.hi, ln.res.lo, oh, ol, N, scale_cols, col_scale, qp ? *qp : QkvPlanes{}, S, D,
-                ln.astat, ln.colsum, ln.rstat, ln.rgamma, ln.rbeta, ln.ostat, ln.parts, ln.inv_dim, ln.emb_T, ln.emb_B,
-                ln.emb_nbranch};
-  ep.stat_cols = ln.stat_cols;
-  if (ln.small) {
+  if (c.parts < 1 || c.parts > (c.small ? 8 : 4)) return fail(MDM_EUNSUPPORTED, "folded LayerNorm: too many partial sums per row (D <= 1024)");
+  ProfScope ps(c.pf, c.prof_cat, 2.0 * M * (double)N * K, s);
+  const X3Epilogue ep = x3_epilogue(c);
+  const bool in_proj = kind == X3K_IN_PROJ_FOLD || kind == X3K_IN_PROJ_PLAIN;
+  if (c.small) {
     // rows are grouped by sequence only where the epilogue needs (sequence, token) -- in_proj's Q / K / V^T planes, InputProcess's
     // (sample, frame); every other GEMM tiles its M rows CONTIGUOUSLY: 197 tokens are three 64-row tiles plus one of 5 rows, i.e.
     // a quarter of the workgroups of a sequence-aligned launch would do 8 % of a tile's work (B = 6: 37 row tiles instead of 48)
-    const int group_rows = (kind == 0 || kind == 6) ? S : (kind == 5 ? ln.emb_T : M);
-    const int rc = launch_gemm_x3s(kind, ln.shape, a, w, ep, M, N, K, group_rows, s);
+    const int group_rows = in_proj ? S : (kind == X3K_EMBED ? c.emb_T : M);
+    const int rc = launch_gemm_x3s(kind, c.shape, c.a, c.w, ep, M, N, K, group_rows, s);
     if (rc == -1 || rc == -3) return lds_fail(rc, "f16x3 linear (small tiles)");
     if (rc == -2) return fail(MDM_EUNSUPPORTED, "f16x3 linear (small tiles): unsupported shape (K must be 288 or a multiple of 256)");
     return rt_launch_status();
   }
-  if (kind == 6) {   // layer 0's in_proj without a folded LayerNorm on the sequence-tile kernel: trans_dec's sequence-tile route (decoder.h)
-    const int rc6 = launch_gemm_x3_qkv(a, w, ep, M / S, S, D, s);
+  if (kind == X3K_IN_PROJ_PLAIN) {   // layer 0's in_proj without a folded LayerNorm on the sequence-tile kernel: trans_dec's sequence-tile route (decoder.h)
+    const int rc6 = launch_gemm_x3_qkv(c.a, c.w, ep, M / S, S, c.D, s);
     if (rc6 != 0) return fail(MDM_EUNSUPPORTED, "f16x3 in_proj: launch failed");
     return rt_launch_status();
   }
-  const int rpt = (kind == 0) ? S : x3_rows_per_tile(M, kind == 5 ? ln.emb_T : S);
-  const int rc = launch_gemm_x3_ln(kind, a, w, ep, M, N, K, rpt, s);
+  const int rpt = (kind == X3K_IN_PROJ_FOLD) ? S : x3_rows_per_tile(M, kind == X3K_EMBED ? c.emb_T : S);
+  const int rc = launch_gemm_x3_ln(kind, c.a, c.w, ep, M, N, K, rpt, s);
   if (rc == -1 || rc == -3) return lds_fail(rc, "f16x3 linear");
   if (rc == -2) return fail(MDM_EUNSUPPORTED, "f16x3 linear: unsupported folded-LayerNorm GEMM kind");
   return rt_launch_status();

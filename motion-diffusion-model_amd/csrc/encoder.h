@@ -14,13 +14,15 @@ int embed_frames_x3(mdm_model* m, const Workspace& ws, const float* x, int B, in
   p16_t* pl = ph + (size_t)B * T * KP;
   MDM_LAUNCH(pose_planes_cond_kernel, dim3(((T + 31) / 32) * (KP / 32) * B + nbranch * B), dim3(256), 0, s, x, ph, pl, T, m->jf, KP, B, ct);
   if (int rc = rt_launch_status()) return rc;
-  LnArgs a;
-  a.res_f32 = m->W("sequence_pos_encoder.pe");
-  a.emb_T = T; a.emb_B = B; a.emb_nbranch = nbranch;
-  a.small = use_small_gemm(m, nbranch * B, T + 1) && KP == 288;
-  a.shape = x3s_shape(m->x3s, nbranch * B);
-  return launch_x3_ln(nullptr, MDM_PROF_EMBED, 5, X3Operand{ph, pl}, m->in_planes, m->W("input_process.poseEmbedding.bias"), a,
-                      nullptr, ws.tokh, ws.tokl, nullptr, B * T, D, KP, T + 1, D, 0, 1.f, s);
+  X3Call c;
+  c.kind = X3K_EMBED; c.prof_cat = MDM_PROF_EMBED;
+  c.a = X3Operand{ph, pl}; c.w = m->in_planes; c.bias = m->W("input_process.poseEmbedding.bias");
+  c.oh = ws.tokh; c.ol = ws.tokl; c.M = B * T; c.N = D; c.K = KP; c.S = T + 1; c.D = D;
+  c.res_f32 = m->W("sequence_pos_encoder.pe");
+  c.emb_T = T; c.emb_B = B; c.emb_nbranch = nbranch;
+  c.small = use_small_gemm(m, nbranch * B, T + 1) && KP == 288;
+  c.shape = x3s_shape(m->x3s, nbranch * B);
+  return launch_x3_ln(c, s);
 }
 inline bool use_embed_x3(const mdm_model* m, int T) {
   // (longer sequences: the row-tile form of the same GEMM where it exists -- 263 features -- else the fp32-operand embedding below)
@@ -28,31 +30,51 @@ inline bool use_embed_x3(const mdm_model* m, int T) {
          (T + 1 <= X3_TM || (use_small_gemm(m, 1, T + 1) && m->jf_k == 288));
 }
 
-// Tokens for every sequence: frame tokens via the InputProcess GEMM, token 0 via cond_token_kernel.
-int embed_tokens(mdm_model* m, const Workspace& ws, const float* x, const long long* timesteps,
-                 long long t_uniform_unused, const float* cond_emb, int B, int T, int nbranch,
-                 int uncond_from_branch, hipStream_t s) {
-  (void)t_uniform_unused;
-  const int D = m->cfg.latent_dim, S = T + 1;
-  PoseGatherLoader al{x, T, m->jf, B * T};
+// InputProcess on the fp32-operand GEMM (gemm_f32.h; x3: its split arithmetic): B samples of T rows each -- frames, behind the
+// C rows of `prefix` if there is one (trans_dec) -- + positional rows, to token rows lead .. lead + T - 1 of every branch's
+// sequences, as fp32 `tok` and, with th / tl, as planes.  lead: 1 (trans_enc: the condition token) or 0.
+int launch_embed_f32(mdm_model* m, float* tok, p16_t* th, p16_t* tl, const float* x, const float* prefix, int C, int B, int T, int lead,
+                     int nbranch, bool x3, hipStream_t s) {
+  const int D = m->cfg.latent_dim;
+  PoseGatherLoader al{x, T, m->jf, B * T, prefix, C};
   RowMajorLoader bl{m->w_in_pad, m->jf_pad, D, m->jf_pad};
+  EmbedEpilogue ep{tok, m->W("input_process.poseEmbedding.bias"), m->W("sequence_pos_encoder.pe"), B, T, T + lead, D, nbranch, th, tl, lead};
+  ProfScope ps(&m->prof, MDM_PROF_EMBED, 2.0 * B * T * (double)D * m->jf, s);
+  launch_gemm_f32(al, bl, ep, B * T, D, m->jf_pad, s, x3);
+  return rt_launch_status();
+}
+
+// Tokens for every sequence: frame tokens via the InputProcess GEMM, token 0 via cond_token_kernel.  The model timestep is
+// per sample (`timesteps`, [B]) or, with timesteps == null, `t_uniform` for all of them (a sampling-loop step).
+int embed_tokens(mdm_model* m, const Workspace& ws, const float* x, const long long* timesteps, int t_uniform,
+                 const float* cond_emb, int B, int T, int nbranch, int uncond_from_branch, hipStream_t s) {
+  const int D = m->cfg.latent_dim, S = T + 1;
   const bool x3 = m->precision == MDM_PREC_F16X3;
-  EmbedEpilogue ep{ws.tok, m->W("input_process.poseEmbedding.bias"), m->W("sequence_pos_encoder.pe"), B, T, S, D,
-                   nbranch, x3 ? ws.tokh : nullptr, x3 ? ws.tokl : nullptr};
   if (use_embed_x3(m, T)) {   // token 0 of every sequence rides in the transpose kernel of the frame embedding: one launch fewer per step
-    const CondTokArgs ct{ws.tok, cond_emb, m->W("embed_text.bias"), m->time_table, timesteps, 0, m->W("sequence_pos_encoder.pe"), B, S, D,
+    const CondTokArgs ct{ws.tok, cond_emb, m->W("embed_text.bias"), m->time_table, timesteps, t_uniform, m->W("sequence_pos_encoder.pe"), B, S, D,
                          uncond_from_branch, (int)m->cfg.max_len, ws.tokh, ws.tokl, m->time_add};
     return embed_frames_x3(m, ws, x, B, T, nbranch, s, ct);
-  } else {
-    ProfScope ps(&m->prof, MDM_PROF_EMBED, 2.0 * B * T * (double)D * m->jf, s);
-    launch_gemm_f32(al, bl, ep, B * T, D, m->jf_pad, s);
   }
-  if (int rc = rt_launch_status()) return rc;
+  if (int rc = launch_embed_f32(m, ws.tok, x3 ? ws.tokh : nullptr, x3 ? ws.tokl : nullptr, x, nullptr, 0, B, T, /*lead=*/1, nbranch,
+                                false, s)) return rc;
   ProfScope ps(&m->prof, MDM_PROF_ELEMENTWISE, 0.0, s);
   MDM_LAUNCH(cond_token_kernel, dim3(nbranch * B), dim3(128), 0, s, ws.tok, cond_emb, m->W("embed_text.bias"),
-             (const float*)m->time_table, timesteps, 0, m->W("sequence_pos_encoder.pe"), B, S, D, uncond_from_branch,
+             (const float*)m->time_table, timesteps, t_uniform, m->W("sequence_pos_encoder.pe"), B, S, D, uncond_from_branch,
              (int)m->cfg.max_len, x3 ? ws.tokh : (p16_t*)nullptr, x3 ? ws.tokl : (p16_t*)nullptr, m->time_add);
   return rt_launch_status();
+}
+
+// What is constant over the GEMMs of one folded-LayerNorm forward (the stack and OutputProcess: who wrote a statistic decides how it is
+// read).  Few sequences: the latency regime -- every GEMM on gemm_x3s.h's 32 / 64-row tiles (row statistics per 128 columns); else
+// gemm_x3.h's sequence-sized tiles (per 256)
+X3Call enc_ln_call(mdm_model* m, int nseq, int S) {
+  const int D = m->cfg.latent_dim;
+  X3Call c; c.M = nseq * S; c.S = S; c.D = D; c.inv_dim = 1.0f / (float)D;
+  c.small = use_small_gemm(m, nseq, S);
+  c.shape = x3s_shape(m->x3s, nseq);
+  c.stat_cols = c.small ? X3S_TN : 256;
+  c.parts = (D + c.stat_cols - 1) / c.stat_cols;
+  return c;
 }
 
 // seqTransEncoder: num_layers post-norm layers over ws.tok [nseq*S, D] (in place).
@@ -65,14 +87,12 @@ int encoder(mdm_model* m, const Workspace& ws, int nseq, int B, int S, const int
     // pre-norm sum, each with per-row partial (sum, sum^2) written by its producer; consumers fold the normalisation
     // (gemm_x3.h X3Epilogue).  Layer 0's input (the embedding) is not normalised: plain in_proj, plain residual.
     const X3Operand xb{ws.tokh, ws.tokl}, xa{ws.xah, ws.xal}, attp{ws.atth, ws.attl}, ffnp{ws.ffnh, ws.ffnl};
-    // few sequences: the latency regime -- every GEMM of the stack on gemm_x3s.h's 32 / 64-row tiles (row statistics per 128
-    // columns); else gemm_x3.h's sequence-sized tiles (per 256)
-    const bool small = use_small_gemm(m, nseq, S);
-    const X3sShape shape = x3s_shape(m->x3s, nseq);
-    const int scols = small ? X3S_TN : 256;
-    const int parts = (D + scols - 1) / scols;
-    const float inv_dim = 1.0f / (float)D;
-    auto LN = [&]() { LnArgs a; a.small = small; a.shape = shape; a.stat_cols = scols; a.parts = parts; a.inv_dim = inv_dim; return a; };
+    const X3Call stack = enc_ln_call(m, nseq, S);
+    const bool small = stack.small;
+    auto LN = [&](X3Kind kind, X3Operand a, X3Weights w, const float* bias, int N, int K) {   // a call site adds what its GEMM has of its own
+      X3Call c = stack; c.kind = kind; c.pf = pf; c.a = a; c.w = w; c.bias = bias; c.N = N; c.K = K;
+      return c;
+    };
     // (Running the stack over two half-batches, so that every producer -> consumer hand-over stays inside the 256 MB Infinity
     // Cache, was built and measured: 1.5 % SLOWER on the same box -- profiles/r02_ab.md -- and removed.)
     // (Running in_proj -> attention and / or linear1 -> linear2 one guidance branch at a time, so that the 352 MB of Q / K / V^T
@@ -86,36 +106,36 @@ int encoder(mdm_model* m, const Workspace& ws, int nseq, int B, int S, const int
       const mdm_model::LayerPlanes& P = m->planes[l];
       const mdm_model::LayerFold& F = m->fold[l];
       if (l == 0 && small) {
-        LnArgs a = LN();
-        if (int rc = launch_x3_ln(pf, MDM_PROF_LINEAR, 6, xb, P.in_proj, m->L(l, "self_attn.in_proj_bias"), a, nullptr, nullptr,
-                                  nullptr, &ws.qp, M, 3 * D, D, S, D, D, qscale, s)) return rc;
+        X3Call c = LN(X3K_IN_PROJ_PLAIN, xb, P.in_proj, m->L(l, "self_attn.in_proj_bias"), 3 * D, D);
+        c.qp = &ws.qp; c.scale_cols = D; c.col_scale = qscale;
+        if (int rc = launch_x3_ln(c, s)) return rc;
       } else if (l == 0) {
         // both guidance branches in one forward: the sequences of a sample differ in token 0 only (embed_frames_x3 writes the frame
         // tokens once, to both), so layer 0's in_proj runs one tile per SAMPLE (gemm_x3.h PAIR; MDM_OPT_ENC_SHARED_LAYER0)
         const int pair_B = (m->enc_shared_l0 && nseq == 2 * B && x3_qkv_pairs(S, D)) ? B : 0;
         if (int rc = launch_in_proj_x3(pf, xb, P.in_proj, m->L(l, "self_attn.in_proj_bias"), ws.qp, nseq, S, D, qscale, s, pair_B)) return rc;
       } else {
-        LnArgs a = LN(); a.astat = ws.stat2; a.colsum = F.c_qkv;
-        if (int rc = launch_x3_ln(pf, MDM_PROF_LINEAR, 0, xb, F.in_proj, F.b_qkv, a, nullptr, nullptr, nullptr, &ws.qp, M,
-                                  3 * D, D, S, D, D, qscale, s)) return rc;
+        X3Call c = LN(X3K_IN_PROJ_FOLD, xb, F.in_proj, F.b_qkv, 3 * D, D);
+        c.astat = ws.stat2; c.colsum = F.c_qkv; c.qp = &ws.qp; c.scale_cols = D; c.col_scale = qscale;
+        if (int rc = launch_x3_ln(c, s)) return rc;
       }
       if (int rc = launch_attention_x3(pf, ws.qp, lengths, nseq, B, S, D, nullptr, ws.atth, ws.attl, s, 1, m->attn_direct)) return rc;
       {  // xa = att.Wo + bo + layer input (normalised on the fly for l >= 1), + row statistics
-        LnArgs a = LN(); a.res = xb; a.ostat = ws.stat1;
-        if (l >= 1) { a.rstat = ws.stat2; a.rgamma = m->L(l - 1, "norm2.weight"); a.rbeta = m->L(l - 1, "norm2.bias"); }
-        if (int rc = launch_x3_ln(pf, MDM_PROF_LINEAR, l == 0 ? 1 : 2, attp, P.out_proj, m->L(l, "self_attn.out_proj.bias"),
-                                  a, nullptr, ws.xah, ws.xal, nullptr, M, D, D, S, D, 0, 1.f, s)) return rc;
+        X3Call c = LN(l == 0 ? X3K_OUT_PROJ_L0 : X3K_OUT_LN_RES, attp, P.out_proj, m->L(l, "self_attn.out_proj.bias"), D, D);
+        c.oh = ws.xah; c.ol = ws.xal; c.res = xb; c.ostat = ws.stat1;
+        if (l >= 1) { c.rstat = ws.stat2; c.rgamma = m->L(l - 1, "norm2.weight"); c.rbeta = m->L(l - 1, "norm2.bias"); }
+        if (int rc = launch_x3_ln(c, s)) return rc;
       }
       {  // ffn = gelu(LN1(xa).W1 + b1), LN1 folded
-        LnArgs a = LN(); a.astat = ws.stat1; a.colsum = F.c_1;
-        if (int rc = launch_x3_ln(pf, MDM_PROF_LINEAR, 3, xa, F.linear1, F.b_1, a, nullptr, ws.ffnh, ws.ffnl, nullptr, M, FF,
-                                  D, S, D, 0, 1.f, s)) return rc;
+        X3Call c = LN(X3K_LINEAR1_GELU, xa, F.linear1, F.b_1, FF, D);
+        c.oh = ws.ffnh; c.ol = ws.ffnl; c.astat = ws.stat1; c.colsum = F.c_1;
+        if (int rc = launch_x3_ln(c, s)) return rc;
       }
       {  // xb = ffn.W2 + b2 + LN1(xa), + row statistics
-        LnArgs a = LN(); a.res = xa; a.rstat = ws.stat1; a.rgamma = m->L(l, "norm1.weight"); a.rbeta = m->L(l, "norm1.bias");
-        a.ostat = ws.stat2;
-        if (int rc = launch_x3_ln(pf, MDM_PROF_LINEAR, 2, ffnp, P.linear2, m->L(l, "linear2.bias"), a, nullptr, ws.tokh,
-                                  ws.tokl, nullptr, M, D, FF, S, D, 0, 1.f, s)) return rc;
+        X3Call c = LN(X3K_OUT_LN_RES, ffnp, P.linear2, m->L(l, "linear2.bias"), D, FF);
+        c.oh = ws.tokh; c.ol = ws.tokl; c.res = xa; c.rstat = ws.stat1; c.rgamma = m->L(l, "norm1.weight"); c.rbeta = m->L(l, "norm1.bias");
+        c.ostat = ws.stat2;
+        if (int rc = launch_x3_ln(c, s)) return rc;
       }
     }
     return 0;   // the encoder's output is LN2(L-1)(xb): folded into OutputProcess (outproj_x3)
@@ -156,6 +176,17 @@ int encoder(mdm_model* m, const Workspace& ws, int nseq, int B, int S, const int
   return 0;
 }
 
+// The transposing / fusing tail of OutputProcess (elementwise.h outproj_finish_kernel) over token rows S - T .. S - 1 of the fp32 rows
+// `out_tok`.  mode 0: every sequence's output, stand-alone; mode 1: the sampler update of a loop step on the B samples (the guidance
+// branches are rows b and B + b), in place on x_t.
+int launch_outproj_finish(mdm_model* m, const float* out_tok, int nseq, int B, int S, int T, const float* scale, int mode, float* out,
+                          float* x0_out, const float* x_t, NoiseSource noise, const unsigned char* inpaint_mask,
+                          const float* inpaint_motion, StepCoefs co, hipStream_t s) {
+  MDM_LAUNCH(outproj_finish_kernel, dim3((T + 31) / 32, (m->jf + 31) / 32, mode == 1 ? B : nseq), dim3(256), 0, s, out_tok,
+             m->jf_out, S, T, m->jf, B, scale, mode, out, x0_out, x_t, noise, inpaint_mask, inpaint_motion, co);
+  return rt_launch_status();
+}
+
 // OutputProcess, split precision: every sequence's tokens x poseFinal -> fp32 rows in the (dead) qkv region, then the
 // transposing / fusing tail kernel (elementwise.h outproj_finish_kernel).
 int outproj_x3(mdm_model* m, const Workspace& ws, int nseq, int B, int T, const float* scale, int mode, float* out,
@@ -165,19 +196,14 @@ int outproj_x3(mdm_model* m, const Workspace& ws, int nseq, int B, int T, const 
   float* out_tok = ws.qkv;
   ProfScope ps(&m->prof, MDM_PROF_OUTPROJ, 2.0 * nseq * T * (double)D * m->jf, s);
   if (m->lnfold && (S <= X3_TM || use_small_gemm(m, nseq, S))) {   // the final LayerNorm is folded into this GEMM
-    LnArgs a; a.astat = ws.stat2; a.colsum = m->c_out; a.inv_dim = 1.0f / (float)D;
-    a.small = use_small_gemm(m, nseq, S);            // (the same decision the encoder took: who wrote stat2)
-    a.shape = x3s_shape(m->x3s, nseq);
-    a.stat_cols = a.small ? X3S_TN : 256;
-    a.parts = (D + a.stat_cols - 1) / a.stat_cols;
-    if (int rc = launch_x3_ln(nullptr, MDM_PROF_OUTPROJ, 4, X3Operand{ws.tokh, ws.tokl}, m->out_planes_f, m->b_out, a,
-                              out_tok, nullptr, nullptr, nullptr, nseq * S, ldo, D, S, D, 0, 1.f, s)) return rc;
+    X3Call c = enc_ln_call(m, nseq, S);            // (the same decisions the encoder took: who wrote stat2)
+    c.kind = X3K_FOLD_F32; c.prof_cat = MDM_PROF_OUTPROJ;
+    c.a = X3Operand{ws.tokh, ws.tokl}; c.w = m->out_planes_f; c.bias = m->b_out; c.out = out_tok; c.N = ldo; c.K = D;
+    c.astat = ws.stat2; c.colsum = m->c_out;
+    if (int rc = launch_x3_ln(c, s)) return rc;
   } else if (int rc = launch_linear_x3(nullptr, X3Operand{ws.tokh, ws.tokl}, m->out_planes, m->out_bias_pad, nullptr, out_tok,
                                        nullptr, nullptr, nseq * S, ldo, D, ACT_NONE, 0, 1.f, S, s)) return rc;
-  const int nb = (mode == 1) ? B : nseq;
-  MDM_LAUNCH(outproj_finish_kernel, dim3((T + 31) / 32, (m->jf + 31) / 32, nb), dim3(256), 0, s, (const float*)out_tok,
-             ldo, S, T, m->jf, B, scale, mode, out, x0_out, x_t, noise, inpaint_mask, inpaint_motion, co);
-  return rt_launch_status();
+  return launch_outproj_finish(m, out_tok, nseq, B, S, T, scale, mode, out, x0_out, x_t, noise, inpaint_mask, inpaint_motion, co, s);
 }
 
 }  // namespace

@@ -1181,34 +1181,39 @@ inline int launch_gemm_x3_w(const X3Operand& A, const X3Weights& W, const X3Epil
   return 0;
 }
 
-// The GEMMs of the folded-LayerNorm encoder:
-//   kind 0  in_proj, A = pre-norm sum           FOLD -> attention operand planes
-//   kind 1  out_proj of layer 0                 residual = plain planes, writes planes + row statistics
-//   kind 2  out_proj (l >= 1) / linear2         residual = LayerNorm rebuilt from planes, writes planes + row statistics
-//   kind 3  linear1                             FOLD + GELU -> planes
-//   kind 4  OutputProcess                       FOLD -> fp32
-//   kind 5  InputProcess                        + positional rows, planes to the token rows of every branch (EMBED)
+// The GEMMs of the folded-LayerNorm stacks (encoder.h, decoder.h): which epilogue a launch_x3_ln call (api_launch.h) runs.  The two
+// dispatchers -- launch_gemm_x3_ln_t here, launch_gemm_x3s_rt in gemm_x3s.h -- map a kind to its kernel instantiation.
+enum X3Kind : int {
+  X3K_IN_PROJ_FOLD = 0,    // in_proj, A = pre-norm sum        FOLD -> attention operand planes
+  X3K_OUT_PROJ_L0 = 1,     // out_proj of layer 0              residual = plain planes, writes planes + row statistics
+  X3K_OUT_LN_RES = 2,      // out_proj (l >= 1) / linear2      residual = LayerNorm rebuilt from planes, writes planes + row statistics
+  X3K_LINEAR1_GELU = 3,    // linear1                          FOLD + GELU -> planes
+  X3K_FOLD_F32 = 4,        // OutputProcess (trans_dec: also the cross-attention q projection)   FOLD -> fp32
+  X3K_EMBED = 5,           // InputProcess                     + positional rows, planes to the token rows of every branch (EMBED)
+  X3K_IN_PROJ_PLAIN = 6,   // in_proj of layer 0               no folded LayerNorm -> attention operand planes (gemm_x3s.h's tiles;
+                           //                                  on this kernel's launch_x3_ln goes through launch_gemm_x3_qkv)
+};
 // TILE: the tile form (X3_T16, X3_PIPE), which launch_gemm_x3_ln chooses by shape
 template <unsigned TILE>
-inline int launch_gemm_x3_ln_t(int kind, const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N,
+inline int launch_gemm_x3_ln_t(X3Kind kind, const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N,
                                    int K, int rpt, hipStream_t s) {
   switch (kind) {
-    case 0: return launch_gemm_x3_w<ACT_NONE, /*RES*/ 0, X3_OUT_QKV | X3_FOLD | TILE>(A, W, ep, M, N, K, rpt, s);
-    case 1: return launch_gemm_x3_w<ACT_NONE, /*RES*/ 2, X3_OUT_PLANES | X3_OSTAT | TILE>(A, W, ep, M, N, K, rpt, s);
-    case 2: return launch_gemm_x3_w<ACT_NONE, /*RES*/ 3, X3_OUT_PLANES | X3_OSTAT | TILE>(A, W, ep, M, N, K, rpt, s);
-    case 3: return launch_gemm_x3_w<ACT_GELU, /*RES*/ 0, X3_OUT_PLANES | X3_FOLD | TILE>(A, W, ep, M, N, K, rpt, s);
-    case 4: return launch_gemm_x3_w<ACT_NONE, /*RES*/ 0, X3_OUT_F32 | X3_FOLD | TILE>(A, W, ep, M, N, K, rpt, s);
-    case 5:   // InputProcess: K = 288 is nine steps -- always the step-synchronous loop
+    case X3K_IN_PROJ_FOLD: return launch_gemm_x3_w<ACT_NONE, /*RES*/ 0, X3_OUT_QKV | X3_FOLD | TILE>(A, W, ep, M, N, K, rpt, s);
+    case X3K_OUT_PROJ_L0: return launch_gemm_x3_w<ACT_NONE, /*RES*/ 2, X3_OUT_PLANES | X3_OSTAT | TILE>(A, W, ep, M, N, K, rpt, s);
+    case X3K_OUT_LN_RES: return launch_gemm_x3_w<ACT_NONE, /*RES*/ 3, X3_OUT_PLANES | X3_OSTAT | TILE>(A, W, ep, M, N, K, rpt, s);
+    case X3K_LINEAR1_GELU: return launch_gemm_x3_w<ACT_GELU, /*RES*/ 0, X3_OUT_PLANES | X3_FOLD | TILE>(A, W, ep, M, N, K, rpt, s);
+    case X3K_FOLD_F32: return launch_gemm_x3_w<ACT_NONE, /*RES*/ 0, X3_OUT_F32 | X3_FOLD | TILE>(A, W, ep, M, N, K, rpt, s);
+    case X3K_EMBED:   // InputProcess: K = 288 is nine steps -- always the step-synchronous loop
       return launch_gemm_x3_w<ACT_NONE, /*RES*/ 1, X3_OUT_PLANES | X3_EMBED | (TILE & X3_T16)>(A, W, ep, M, N, K, rpt, s);
     default: return -2;
   }
 }
 // 208-row tiles whenever the row extent of a tile fits (S = 197 does); on them the pipelined loop wherever it exists (an even
 // number of 32-deep k steps; not InputProcess)
-inline int launch_gemm_x3_ln(int kind, const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N,
+inline int launch_gemm_x3_ln(X3Kind kind, const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N,
                                  int K, int rpt, hipStream_t s) {
   if (rpt <= X3_TM - 16) {
-    if (kind != 5 && (K / X3_BK) % 2 == 0) return launch_gemm_x3_ln_t<X3_T16 | X3_PIPE>(kind, A, W, ep, M, N, K, rpt, s);
+    if (kind != X3K_EMBED && (K / X3_BK) % 2 == 0) return launch_gemm_x3_ln_t<X3_T16 | X3_PIPE>(kind, A, W, ep, M, N, K, rpt, s);
     return launch_gemm_x3_ln_t<X3_T16>(kind, A, W, ep, M, N, K, rpt, s);
   }
   return launch_gemm_x3_ln_t<0u>(kind, A, W, ep, M, N, K, rpt, s);

@@ -549,26 +549,26 @@ inline int launch_gemm_x3s_t(const X3Operand& A, const X3Weights& W, const X3Epi
   return 0;
 }
 
-// the GEMM kinds of launch_gemm_x3_ln (gemm_x3.h), plus kind 6 = layer 0's in_proj (no folded LayerNorm)
+// the GEMM kinds on the row tiles: gemm_x3.h X3Kind (the table lives there)
 template <int RT>
-inline int launch_gemm_x3s_rt(int kind, const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N, int K,
+inline int launch_gemm_x3s_rt(X3Kind kind, const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N, int K,
                               int group_rows, hipStream_t s) {
   // K-chunks of 128 k (8 sub-steps): 16 / 32 KB per buffer.  (256-k chunks for the 32-row tiles measured 1.5-4 % slower: 22.2 /
   // 37.3 / 52.7 vs 21.9 / 36.6 / 50.5 ms at B = 1 / 6 / 10; a third resident workgroup per CU changed nothing: r4lat5)
   constexpr int NS = 8;
   switch (kind) {
-    case 0: return launch_gemm_x3s_t<RT, NS, true, ACT_NONE, /*RES*/ 0, X3_OUT_QKV | X3_FOLD>(A, W, ep, M, N, K, group_rows, s);
-    case 6: return launch_gemm_x3s_t<RT, NS, true, ACT_NONE, /*RES*/ 0, X3_OUT_QKV>(A, W, ep, M, N, K, group_rows, s);
-    case 1: return launch_gemm_x3s_t<RT, NS, true, ACT_NONE, /*RES*/ 2, X3_OUT_PLANES | X3_OSTAT>(A, W, ep, M, N, K, group_rows, s);
-    case 2: return launch_gemm_x3s_t<RT, NS, true, ACT_NONE, /*RES*/ 3, X3_OUT_PLANES | X3_OSTAT>(A, W, ep, M, N, K, group_rows, s);
-    case 3: return launch_gemm_x3s_t<RT, NS, true, ACT_GELU, /*RES*/ 0, X3_OUT_PLANES | X3_FOLD>(A, W, ep, M, N, K, group_rows, s);
-    case 4: return launch_gemm_x3s_t<RT, NS, true, ACT_NONE, /*RES*/ 0, X3_OUT_F32 | X3_FOLD>(A, W, ep, M, N, K, group_rows, s);
-    case 5:   // InputProcess: K = 288 (263 features padded to 9 x 32) is one chunk of 18 sub-steps
+    case X3K_IN_PROJ_FOLD: return launch_gemm_x3s_t<RT, NS, true, ACT_NONE, /*RES*/ 0, X3_OUT_QKV | X3_FOLD>(A, W, ep, M, N, K, group_rows, s);
+    case X3K_IN_PROJ_PLAIN: return launch_gemm_x3s_t<RT, NS, true, ACT_NONE, /*RES*/ 0, X3_OUT_QKV>(A, W, ep, M, N, K, group_rows, s);
+    case X3K_OUT_PROJ_L0: return launch_gemm_x3s_t<RT, NS, true, ACT_NONE, /*RES*/ 2, X3_OUT_PLANES | X3_OSTAT>(A, W, ep, M, N, K, group_rows, s);
+    case X3K_OUT_LN_RES: return launch_gemm_x3s_t<RT, NS, true, ACT_NONE, /*RES*/ 3, X3_OUT_PLANES | X3_OSTAT>(A, W, ep, M, N, K, group_rows, s);
+    case X3K_LINEAR1_GELU: return launch_gemm_x3s_t<RT, NS, true, ACT_GELU, /*RES*/ 0, X3_OUT_PLANES | X3_FOLD>(A, W, ep, M, N, K, group_rows, s);
+    case X3K_FOLD_F32: return launch_gemm_x3s_t<RT, NS, true, ACT_NONE, /*RES*/ 0, X3_OUT_F32 | X3_FOLD>(A, W, ep, M, N, K, group_rows, s);
+    case X3K_EMBED:   // InputProcess: K = 288 (263 features padded to 9 x 32) is one chunk of 18 sub-steps
       return launch_gemm_x3s_t<RT, 18, false, ACT_NONE, /*RES*/ 1, X3_OUT_PLANES | X3_EMBED>(A, W, ep, M, N, K, group_rows, s);
     default: return -2;
   }
 }
-inline int launch_gemm_x3s(int kind, X3sShape sh, const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N, int K,
+inline int launch_gemm_x3s(X3Kind kind, X3sShape sh, const X3Operand& A, const X3Weights& W, const X3Epilogue& ep, int M, int N, int K,
                            int group_rows, hipStream_t s) {
   if (sh.rt == 1) return launch_gemm_x3s_rt<1>(kind, A, W, ep, M, N, K, group_rows, s);
   return launch_gemm_x3s_rt<2>(kind, A, W, ep, M, N, K, group_rows, s);

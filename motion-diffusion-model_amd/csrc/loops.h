@@ -4,6 +4,24 @@
 #pragma once
 // (included inside mdm_api.hip's extern "C" block: these ARE exported entry points of include/mdm_hip.h)
 
+namespace {
+// What both loops ask of their mdm_sample_params_t, in the order both report it: schedule tables, start_index, inpainting pair, CFG
+// needs text, dump buffers, timestep range.  `who` is the entry point, `text` what it calls its text input.
+int check_loop_params(const mdm_model_t* m, const mdm_sample_params_t* p, const char* who, const char* text) {
+  const std::string w(who);
+  if (p->num_timesteps <= 0 || p->start_index < 0 || p->start_index >= p->num_timesteps)
+    return fail(MDM_EINVAL, w + ": bad start_index / num_timesteps");
+  if (!p->a_x0 || !p->a_xt || !p->sigma || !p->timestep_map) return fail(MDM_EINVAL, w + ": null schedule table");
+  if ((p->inpaint_mask_dev == nullptr) != (p->inpaint_motion_dev == nullptr))
+    return fail(MDM_EINVAL, w + ": inpainting needs mask and motion");
+  if (p->scale_dev != nullptr && p->text_embed_dev == nullptr) return fail(MDM_EINVAL, w + ": CFG needs " + text);
+  if (p->num_dump > 0 && (p->dump_steps == nullptr || p->dump_dev == nullptr)) return fail(MDM_EINVAL, w + ": dump buffers missing");
+  for (int i = 0; i <= p->start_index; ++i)
+    if (p->timestep_map[i] < 0 || p->timestep_map[i] >= m->cfg.max_len) return fail(MDM_EINVAL, w + ": timestep outside the positional table");
+  return MDM_OK;
+}
+}  // namespace
+
 int mdm_sample_loop(mdm_model_t* m, const mdm_sample_params_t* p, float* x, void* ws_dev, size_t ws_bytes,
                     void* stream) {
   ChainGuard chain_guard(stream);
@@ -14,17 +32,9 @@ int mdm_sample_loop(mdm_model_t* m, const mdm_sample_params_t* p, float* x, void
   TimeAddScope time_add(m, B, "mdm_sample_loop");
   if (time_add.rc) return time_add.rc;
   if (B <= 0 || T <= 0 || T + 1 > m->cfg.max_len) return fail(MDM_EINVAL, "mdm_sample_loop: need B >= 1 and 1 <= T < the positional table's length");
-  if (p->num_timesteps <= 0 || p->start_index < 0 || p->start_index >= p->num_timesteps)
-    return fail(MDM_EINVAL, "mdm_sample_loop: bad start_index / num_timesteps");
-  if (!p->a_x0 || !p->a_xt || !p->sigma || !p->timestep_map) return fail(MDM_EINVAL, "mdm_sample_loop: null schedule table");
-  if ((p->inpaint_mask_dev == nullptr) != (p->inpaint_motion_dev == nullptr))
-    return fail(MDM_EINVAL, "mdm_sample_loop: inpainting needs mask and motion");
+  if (int rc = check_loop_params(m, p, "mdm_sample_loop", "text_embed")) return rc;
   const bool cfg = p->scale_dev != nullptr;
   const bool uncond_only = !cfg && (p->force_uncond || p->text_embed_dev == nullptr);
-  if (cfg && p->text_embed_dev == nullptr) return fail(MDM_EINVAL, "mdm_sample_loop: CFG needs text_embed");
-  if (p->num_dump > 0 && (p->dump_steps == nullptr || p->dump_dev == nullptr)) return fail(MDM_EINVAL, "mdm_sample_loop: dump buffers missing");
-  for (int i = 0; i <= p->start_index; ++i)
-    if (p->timestep_map[i] < 0 || p->timestep_map[i] >= m->cfg.max_len) return fail(MDM_EINVAL, "mdm_sample_loop: timestep outside the positional table");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nbranch = cfg ? 2 : 1, nseq = nbranch * B, S = T + 1, D = m->cfg.latent_dim;
   Workspace ws = carve(m, nseq, T, ws_dev);
@@ -42,30 +52,7 @@ int mdm_sample_loop(mdm_model_t* m, const mdm_sample_params_t* p, float* x, void
   int dump_i = 0, k = 0;
   for (int i = p->start_index; i >= 0; --i, ++k) {
     // frame tokens + condition token for model timestep timestep_map[i]
-    {
-      PoseGatherLoader al{x, T, m->jf, B * T};
-      RowMajorLoader bl{m->w_in_pad, m->jf_pad, D, m->jf_pad};
-      const bool x3 = m->precision == MDM_PREC_F16X3;
-      EmbedEpilogue ep{ws.tok, m->W("input_process.poseEmbedding.bias"), m->W("sequence_pos_encoder.pe"), B, T, S, D, nbranch,
-                       x3 ? ws.tokh : nullptr, x3 ? ws.tokl : nullptr};
-      if (use_embed_x3(m, T)) {   // (token 0 of every sequence rides in the transpose kernel of the frame embedding)
-        const CondTokArgs ct{ws.tok, ws.cond, m->W("embed_text.bias"), m->time_table, nullptr, (int)p->timestep_map[i],
-                             m->W("sequence_pos_encoder.pe"), B, S, D, uncond_from, (int)m->cfg.max_len, ws.tokh, ws.tokl, m->time_add};
-        if (int rc = embed_frames_x3(m, ws, x, B, T, nbranch, s, ct)) return rc;
-      } else {
-        {
-          ProfScope ps(&m->prof, MDM_PROF_EMBED, 2.0 * B * T * (double)D * m->jf, s);
-          launch_gemm_f32(al, bl, ep, B * T, D, m->jf_pad, s);
-        }
-        if (int rc = rt_launch_status()) return rc;
-        ProfScope ps(&m->prof, MDM_PROF_ELEMENTWISE, 0.0, s);
-        MDM_LAUNCH(cond_token_kernel, dim3(nseq), dim3(128), 0, s, ws.tok, (const float*)ws.cond,
-                   m->W("embed_text.bias"), (const float*)m->time_table, (const long long*)nullptr,
-                   (int)p->timestep_map[i], m->W("sequence_pos_encoder.pe"), B, S, D, uncond_from,
-                   (int)m->cfg.max_len, x3 ? ws.tokh : (p16_t*)nullptr, x3 ? ws.tokl : (p16_t*)nullptr, m->time_add);
-        if (int rc = rt_launch_status()) return rc;
-      }
-    }
+    if (int rc = embed_tokens(m, ws, x, nullptr, (int)p->timestep_map[i], ws.cond, B, T, nbranch, uncond_from, s)) return rc;
     if (int rc = encoder(m, ws, nseq, B, S, len, s)) return rc;
     // this step's eps: injected, or the counter-based stream -- drawn inline by the split-precision tail kernel, into the
     // (now dead) attention buffer for the exact-fp32 OutputProcess epilogue
@@ -123,17 +110,9 @@ int mdm_sample_loop_dec(mdm_model_t* m, const mdm_sample_dec_params_t* pd, float
   if (time_add.rc) return time_add.rc;
   if (int rc = check_dec_shapes(m, "mdm_sample_loop_dec", pd->prefix_dev, B, P, ntok)) return rc;
   if (pd->text_lengths_dev == nullptr) return fail(MDM_EINVAL, "mdm_sample_loop_dec: text_lengths required");
-  if (p->num_timesteps <= 0 || p->start_index < 0 || p->start_index >= p->num_timesteps)
-    return fail(MDM_EINVAL, "mdm_sample_loop_dec: bad start_index / num_timesteps");
-  if (!p->a_x0 || !p->a_xt || !p->sigma || !p->timestep_map) return fail(MDM_EINVAL, "mdm_sample_loop_dec: null schedule table");
-  if ((p->inpaint_mask_dev == nullptr) != (p->inpaint_motion_dev == nullptr))
-    return fail(MDM_EINVAL, "mdm_sample_loop_dec: inpainting needs mask and motion");
+  if (int rc = check_loop_params(m, p, "mdm_sample_loop_dec", "the text tokens")) return rc;
   const bool cfg = p->scale_dev != nullptr;
   const bool uncond_only = !cfg && (p->force_uncond || p->text_embed_dev == nullptr);
-  if (cfg && p->text_embed_dev == nullptr) return fail(MDM_EINVAL, "mdm_sample_loop_dec: CFG needs the text tokens");
-  if (p->num_dump > 0 && (p->dump_steps == nullptr || p->dump_dev == nullptr)) return fail(MDM_EINVAL, "mdm_sample_loop_dec: dump buffers missing");
-  for (int i = 0; i <= p->start_index; ++i)
-    if (p->timestep_map[i] < 0 || p->timestep_map[i] >= m->cfg.max_len) return fail(MDM_EINVAL, "mdm_sample_loop_dec: timestep outside the positional table");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int branches = cfg ? MDM_BRANCH_BOTH : (uncond_only ? MDM_BRANCH_UNCOND : MDM_BRANCH_COND);
   const int nbranch = cfg ? 2 : 1, nseq = nbranch * B, D = m->cfg.latent_dim, L = m->cfg.num_layers;

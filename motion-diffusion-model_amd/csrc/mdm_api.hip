@@ -458,7 +458,7 @@ int mdm_forward(mdm_model_t* m, const float* x, const int64_t* timesteps, const 
     if (int rc = launch_linear(nullptr, text_embed, m->cfg.clip_dim, m->W("embed_text.weight"), m->W("embed_text.bias"), nullptr,
                                ws.cond, B, D, m->cfg.clip_dim, ACT_NONE, 0, 1.f, s)) return rc;
   const int uncond_from = (branches == MDM_BRANCH_UNCOND) ? 0 : 1;
-  if (int rc = embed_tokens(m, ws, x, reinterpret_cast<const long long*>(timesteps), 0, ws.cond, B, T, nbranch,
+  if (int rc = embed_tokens(m, ws, x, reinterpret_cast<const long long*>(timesteps), /*t_uniform=*/0, ws.cond, B, T, nbranch,
                             uncond_from, s)) return rc;
   if (int rc = encoder(m, ws, nseq, B, S, len, s)) return rc;
   // OutputProcess, plain: every branch's tokens -> [nseq, JF, T]
@@ -706,8 +706,9 @@ int mdm_linear_f16f6(const float* in, const float* w, const float* bias, const f
     if (int rc = rt_launch_status()) return rc;
   }
   if (fast) {
-    X3Epilogue ep{out, bias, res, nullptr, nullptr, nullptr, nullptr, N, 0, 1.f, QkvPlanes{}, 0, 0,
-                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1.f, 1, 1, 1, 1.f};
+    X3Call c; c.out = out; c.bias = bias; c.res_f32 = res; c.N = N;
+    X3Epilogue ep = x3_epilogue(c);
+    ep.acc_scale = 1.f;   // (pack_weight_f16f6_kernel's planes are unscaled: no 2^8 to undo)
     const X3Operand a{reinterpret_cast<const p16_t*>(pa.h16), reinterpret_cast<const p16_t*>(pa.rec)};
     const int rc = launch_gemm_f16f6(a, X3Weights{wfh, wfl}, ep, M, N, K, act, s);
     if (rc == -1 || rc == -3) return lds_fail(rc, "mdm_linear_f16f6");
