@@ -501,6 +501,52 @@ int mdm_eval_text_embeddings(const mdm_eval_model_t* model, const float* word_em
                              const int32_t* cap_lens_dev, float* out_dev, int32_t B, int32_t L, int32_t max_len,
                              void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The DistilBERT text encoder of the `text_encoder_type='bert'` checkpoints (model/BERT/BERT_encoder.py: HF DistilBertModel, eval mode):
+ * token ids -> last_hidden_state, in exact fp32 (additive to ABI 10; kernels: csrc/text_encoder.h).
+ *   x0 = LN(word_emb[id] + pos_emb[t]);  per layer: q, k, v = x W^T + b, heads of 64, p = softmax(q k^T / 8 over keys t' < lens[b]),
+ *   x = LN(ctx Wo^T + bo + x), x = LN(gelu_erf(x W1^T + b1) W2^T + b2 + x);  every LN with ln_eps (DistilBERT: 1e-12).
+ * Every weight is a caller-owned, 16-byte aligned fp32 DEVICE array, prepared once per model (mdm_amd/text_encoder.py does it).
+ *
+ * One layer (HF names under transformer.layer.N):
+ *   qkv_w [3 dim][dim], qkv_b [3 dim]     attention.q_lin, k_lin, v_lin stacked in that order, the q rows (weight AND bias) already
+ *                                         multiplied by 1/8 = 1/sqrt(64)
+ *   out_w [dim][dim], out_b [dim]         attention.out_lin          sa_ln_g, sa_ln_b [dim]     sa_layer_norm
+ *   lin1_w [hidden][dim], lin1_b [hidden] ffn.lin1                   lin2_w [dim][hidden], lin2_b [dim]   ffn.lin2
+ *   out_ln_g, out_ln_b [dim]              output_layer_norm */
+typedef struct mdm_text_layer {
+  const float* qkv_w; const float* qkv_b;
+  const float* out_w; const float* out_b;
+  const float* sa_ln_g; const float* sa_ln_b;
+  const float* lin1_w; const float* lin1_b;
+  const float* lin2_w; const float* lin2_b;
+  const float* out_ln_g; const float* out_ln_b;
+} mdm_text_layer_t;
+
+/* word_emb [vocab][dim], pos_emb [max_pos][dim], emb_ln_g / emb_ln_b [dim]: embeddings.word_embeddings, position_embeddings,
+ * LayerNorm.  layers: a HOST array of n_layers structs.  dim == 64 n_heads and dim <= 1024; hidden a positive multiple of 4;
+ * 1 <= n_layers <= 16; vocab >= 1; max_pos >= 1. */
+typedef struct mdm_text_model {
+  const float* word_emb; const float* pos_emb;
+  const float* emb_ln_g; const float* emb_ln_b;
+  const mdm_text_layer_t* layers;
+  int32_t n_layers, dim, n_heads, hidden, vocab, max_pos;
+  float ln_eps;
+} mdm_text_model_t;
+
+/* Bytes of workspace mdm_text_encode needs for B prompts padded to L word pieces; 0 on a bad argument (mdm_last_error says which).
+ * In floats: B L (5 dim + hidden)  -- the token rows, their q | k | v, the attention output and the feed-forward's hidden rows --
+ * plus 64 bytes. */
+size_t mdm_text_workspace_bytes(const mdm_text_model_t* model, int32_t B, int32_t L);
+
+/* ids_dev [B, L] int32 (right-padded prompts), lens_dev [B] int32 valid word pieces per prompt -> out_dev [B, L, dim], or
+ * [L, B, dim] with token_major != 0 (what the decoder's memory wants).  Rows at or beyond a length are written as zeros; the ids
+ * behind a length are not read, and a valid row does not depend on L, on B or on the other prompts (bit for bit).
+ * 1 <= L <= min(128, max_pos).  lens[b] in [1, L] and ids < vocab are the caller's duty (a host tokenizer made them; an id outside
+ * the table is clamped into it, a length outside [0, L] likewise).  workspace_dev: at least mdm_text_workspace_bytes.
+ * 7 launches per layer and one for the embeddings.  No device allocation, no synchronisation, every kernel on `stream`: capture-safe. */
+int mdm_text_encode(const mdm_text_model_t* model, const int32_t* ids_dev, const int32_t* lens_dev, float* out_dev, int32_t B,
+                    int32_t L, int32_t token_major, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = [
     "mdm_sample_loop_dec", "mdm_weights_in_range", "mdm_set_option", "mdm_get_option", "mdm_set_time_add",
     "mdm_rot6d_to_smpl_joints", "mdm_smpl_workspace_bytes", "mdm_smpl_forward",
     "mdm_eval_workspace_bytes", "mdm_eval_motion_embeddings", "mdm_eval_text_embeddings",
+    "mdm_text_workspace_bytes", "mdm_text_encode",
 ]
 # include/mdm_hip_probe.h: exported by the probe build only
 PROBE_SYMBOLS = ["mdm_debug_set", "mdm_debug_get", "mdm_linear_f16f6", "mdm_linear_f16f6_scratch_bytes", "mdm_probe_in_proj"]
@@ -65,6 +66,18 @@ class MdmEvalModel(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "out_w", "out_b", "pos_w", "pos_b")] + \
                [("motion", MdmEvalGru), ("text", MdmEvalGru)] + \
                [(n, C.c_int32) for n in ("dim_pose", "conv_hidden", "latent", "word", "pos", "unit_length")]
+
+
+class MdmTextLayer(C.Structure):
+    """include/mdm_hip.h mdm_text_layer_t: one DistilBERT layer (q | k | v stacked, the q rows pre-scaled by 1/8)."""
+    _fields_ = [(n, C.c_void_p) for n in ("qkv_w", "qkv_b", "out_w", "out_b", "sa_ln_g", "sa_ln_b", "lin1_w", "lin1_b", "lin2_w",
+                                          "lin2_b", "out_ln_g", "out_ln_b")]
+
+
+class MdmTextModel(C.Structure):
+    """include/mdm_hip.h mdm_text_model_t."""
+    _fields_ = [(n, C.c_void_p) for n in ("word_emb", "pos_emb", "emb_ln_g", "emb_ln_b")] + [("layers", C.POINTER(MdmTextLayer))] + \
+               [(n, C.c_int32) for n in ("n_layers", "dim", "n_heads", "hidden", "vocab", "max_pos")] + [("ln_eps", C.c_float)]
 
 
 SMPL_POSE_REPS = {"rot6d": 0, "rotvec": 1, "rotmat": 2, "rotquat": 3}      # MDM_SMPL_*: feature counts 6, 3, 9, 4
@@ -150,6 +163,8 @@ class MdmLib:
             "mdm_eval_workspace_bytes": (sz, [P(MdmEvalModel), i32, i32, i32]),
             "mdm_eval_motion_embeddings": (C.c_int, [P(MdmEvalModel), vp, vp, vp, i32, i32, i32, vp, sz, vp]),
             "mdm_eval_text_embeddings": (C.c_int, [P(MdmEvalModel), vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+            "mdm_text_workspace_bytes": (sz, [P(MdmTextModel), i32, i32]),
+            "mdm_text_encode": (C.c_int, [P(MdmTextModel), vp, vp, vp, i32, i32, i32, vp, sz, vp]),
         }
         probe_sig = {
             "mdm_debug_set": (C.c_int, [C.c_int, C.c_int]),

@@ -34,6 +34,7 @@
 #include "smpl_joints.h"
 #include "smpl_mesh.h"
 #include "evaluator.h"
+#include "text_encoder.h"
 
 using namespace mdm;
 
@@ -1156,6 +1157,118 @@ int mdm_eval_text_embeddings(const mdm_eval_model_t* m, const float* word_embs, 
   }
   if (int rc = eval_linear(inp, m->text.in_w, m->text.in_b, emb, B * L, Ht, W, s)) return rc;
   return eval_gru_encode(m->text, emb, cap_lens, 1, max_len > 0 ? max_len : L, gi, h, o1, out, B, L, s);
+}
+
+}  // extern "C"
+
+namespace {
+
+// Validation shared by mdm_text_workspace_bytes and mdm_text_encode; 0 or a negative code with the message set (it names the field)
+int text_plan(const char* fn, const mdm_text_model_t* m, int B, int L, size_t& floats) {
+  const std::string f = std::string(fn) + ": ";
+  if (m == nullptr) return fail(MDM_EINVAL, f + "null model");
+  if (B < 1) return fail(MDM_EINVAL, f + "B must be at least 1");
+  if (L < 1) return fail(MDM_EINVAL, f + "L must be at least 1 word piece");
+  if (L > TXT_MAX_L) return fail(MDM_EUNSUPPORTED, f + "L must be at most 128 word pieces (the attention kernel keeps 4 key tiles of 32)");
+  if (m->max_pos < 1) return fail(MDM_EINVAL, f + "max_pos must be at least 1");
+  if (L > m->max_pos) return fail(MDM_EINVAL, f + "L exceeds max_pos, the rows of the position table (" + std::to_string(m->max_pos) + ")");
+  if (m->n_heads < 1 || m->dim != TXT_HD * m->n_heads) return fail(MDM_EUNSUPPORTED, f + "dim must equal 64 * n_heads (heads of 64)");
+  if (m->dim > TXT_MAX_DIM) return fail(MDM_EUNSUPPORTED, f + "dim must be at most 1024 (the LayerNorm rows)");
+  if (m->hidden < 4 || m->hidden % 4 != 0) return fail(MDM_EUNSUPPORTED, f + "hidden must be a positive multiple of 4");
+  if (m->n_layers < 1 || m->n_layers > 16) return fail(MDM_EUNSUPPORTED, f + "n_layers must be between 1 and 16");
+  if (m->vocab < 1) return fail(MDM_EINVAL, f + "vocab must be at least 1");
+  if (!(m->ln_eps >= 0.f)) return fail(MDM_EINVAL, f + "ln_eps must be >= 0");
+  auto check = [&](const float* q, const std::string& name) {
+    if (q == nullptr) return fail(MDM_EINVAL, f + "null weight pointer " + name);
+    if ((reinterpret_cast<uintptr_t>(q) & 15) != 0) return fail(MDM_EINVAL, f + "weight pointer " + name + " must be 16-byte aligned");
+    return 0;
+  };
+  const float* top[] = {m->word_emb, m->pos_emb, m->emb_ln_g, m->emb_ln_b};
+  const char* top_names[] = {"word_emb", "pos_emb", "emb_ln_g", "emb_ln_b"};
+  for (int i = 0; i < 4; ++i)
+    if (int rc = check(top[i], top_names[i])) return rc;
+  if (m->layers == nullptr) return fail(MDM_EINVAL, f + "null layers");
+  static const char* layer_names[] = {"qkv_w", "qkv_b", "out_w", "out_b", "sa_ln_g", "sa_ln_b", "lin1_w", "lin1_b", "lin2_w", "lin2_b", "out_ln_g", "out_ln_b"};
+  for (int l = 0; l < m->n_layers; ++l) {
+    const mdm_text_layer_t& y = m->layers[l];
+    const float* ptrs[] = {y.qkv_w, y.qkv_b, y.out_w, y.out_b, y.sa_ln_g, y.sa_ln_b, y.lin1_w, y.lin1_b, y.lin2_w, y.lin2_b, y.out_ln_g, y.out_ln_b};
+    for (int i = 0; i < 12; ++i)
+      if (int rc = check(ptrs[i], "layers[" + std::to_string(l) + "]." + layer_names[i])) return rc;
+  }
+  // (row counts and offsets inside the GEMMs are 32-bit)
+  if ((int64_t)B * L * std::max<int64_t>(3 * (int64_t)m->dim, m->hidden) >= (1ll << 31))
+    return fail(MDM_EUNSUPPORTED, f + "B too large for one call: chunk the prompts (a row's result does not depend on the batch)");
+  floats = (size_t)B * L * (5 * (size_t)m->dim + m->hidden);
+  return 0;
+}
+
+// One dense layer of the encoder on gemm_f32.h's exact-fp32 kernel.  launch_gemm_f32_t sends an output of fewer than 64 x 64 x 4
+// elements to its 128-row tiles: a one-prompt call's out_lin and lin2 (12 x 768) would be 6 workgroups walking K = 768 / 3072 alone,
+// 138 us a launch and 80 % of the call (profiles/r14a_text_encoder.md).  Those go to the 64-row tiles here -- twice the workgroups;
+// both tile shapes sum k in one order, so a row keeps its bits whichever one a batch size selects.
+int text_linear(const float* in, const float* w, const float* bias, const float* res, float* out, int M, int N, int K, int act,
+                hipStream_t s) {
+  if ((size_t)M * N >= 64 * 64 * 4) return launch_linear(nullptr, in, K, w, bias, res, out, M, N, K, act, 0, 1.f, s);
+  RowMajorLoader al{in, K, M, K};
+  RowMajorLoader bl{w, K, N, K};
+  LinearEpilogue ep{out, bias, res, N, act, 0, 1.f, nullptr, nullptr};
+  const int tm = (M + 63) / 64, tn = (N + 63) / 64;
+  auto kfn = &gemm_f32_kernel<RowMajorLoader, RowMajorLoader, LinearEpilogue, 64, false, 1>;
+  MDM_LAUNCH(kfn, dim3(tm * tn), dim3(GEMM_THREADS), gemm_f32_lds_total(64, false), s, al, bl, ep, M, N, K, tn, 0);
+  return rt_launch_status();
+}
+
+int text_ln(TextLnArgs a, hipStream_t s) {
+  auto k = &text_ln_kernel;
+  MDM_LAUNCH(k, dim3((unsigned)((a.B * a.L + 3) / 4)), dim3(256), 0, s, a);
+  return rt_launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mdm_text_workspace_bytes(const mdm_text_model_t* model, int32_t B, int32_t L) {
+  size_t floats = 0;
+  if (text_plan("mdm_text_workspace_bytes", model, B, L, floats) != 0) return 0;
+  return floats * sizeof(float) + 64;
+}
+
+int mdm_text_encode(const mdm_text_model_t* m, const int32_t* ids, const int32_t* lens, float* out, int32_t B, int32_t L,
+                    int32_t token_major, void* ws, size_t ws_bytes, void* stream) {
+  size_t floats = 0;
+  if (int rc = text_plan("mdm_text_encode", m, B, L, floats)) return rc;
+  if (!ids || !lens || !out || !ws) return fail(MDM_EINVAL, "mdm_text_encode: null ids_dev, lens_dev, out_dev or workspace_dev");
+  if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) return fail(MDM_EINVAL, "mdm_text_encode: out_dev must be 16-byte aligned");
+  if (ws_bytes < floats * sizeof(float) + 64) return fail(MDM_ENOSPC, "mdm_text_encode: workspace_bytes too small (mdm_text_workspace_bytes)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ChainGuard chain_guard(stream);
+  const int D = m->dim, H = m->n_heads, FF = m->hidden, M = B * L;
+  float* x = eval_ws(ws);                      // [M][D] the token rows (residual stream)
+  float* qkv = x + (size_t)M * D;              // [M][3D]
+  float* ctx = qkv + (size_t)M * 3 * D;        // [M][D]
+  float* ffn = ctx + (size_t)M * D;            // [M][FF]
+  TextLnArgs ln{nullptr, ids, m->word_emb, m->pos_emb, m->emb_ln_g, m->emb_ln_b, lens, x, B, L, D, m->vocab, m->ln_eps, 0};
+  if (int rc = text_ln(ln, s)) return rc;
+  ln.ids = nullptr;
+  ln.in = x;
+  auto attn_k = &text_attn_kernel;
+  const int nqt = (L + 31) / 32;
+  for (int l = 0; l < m->n_layers; ++l) {
+    const mdm_text_layer_t& y = m->layers[l];
+    const bool last = l + 1 == m->n_layers;
+    if (int rc = text_linear(x, y.qkv_w, y.qkv_b, nullptr, qkv, M, 3 * D, D, ACT_NONE, s)) return rc;
+    MDM_LAUNCH(attn_k, dim3((unsigned)(B * H * nqt)), dim3(64), text_attn_lds_bytes(L), s, (const float*)qkv, lens, ctx, (int)L, D, H);
+    if (int rc = rt_launch_status()) return rc;
+    if (int rc = text_linear(ctx, y.out_w, y.out_b, x, x, M, D, D, ACT_NONE, s)) return rc;    // + x, in place
+    ln.gamma = y.sa_ln_g; ln.beta = y.sa_ln_b; ln.out = x; ln.token_major = 0;
+    if (int rc = text_ln(ln, s)) return rc;
+    if (int rc = text_linear(x, y.lin1_w, y.lin1_b, nullptr, ffn, M, FF, D, ACT_GELU, s)) return rc;
+    if (int rc = text_linear(ffn, y.lin2_w, y.lin2_b, x, x, M, D, FF, ACT_NONE, s)) return rc;   // + x, in place
+    ln.gamma = y.out_ln_g; ln.beta = y.out_ln_b; ln.out = last ? out : x; ln.token_major = last ? (token_major != 0) : 0;
+    if (int rc = text_ln(ln, s)) return rc;
+  }
+  return MDM_OK;
 }
 
 }  // extern "C"

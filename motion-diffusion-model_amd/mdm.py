@@ -23,6 +23,7 @@ from . import _native as nat
 from . import _engine
 from ._engine import Engine
 from .rotation2xyz import Rotation2xyz
+from .text_encoder import BERT, load_bert
 
 
 class PositionalEncoding(nn.Module):
@@ -267,8 +268,15 @@ class MDM(nn.Module):
             self.embed_action = EmbedAction(self.num_actions, latent_dim)
         if 'text' in self.cond_mode:
             self.embed_text = nn.Linear(clip_dim, latent_dim)
-            # the text encoder itself (CLIP / DistilBERT) is outside the hot path: callers cache y['text_embed']
-            self.clip_model = self._try_load_clip(clip_version) if self.text_encoder_type == 'clip' else None
+            # CLIP is outside the hot path (callers cache y['text_embed']); DistilBERT runs on it when `bert_model_path` names a
+            # local HF model directory (mdm_amd/text_encoder.py; model/mdm.py:119 `self.clip_model = load_bert(bert_model_path)`)
+            bert_model_path = kargs.get('bert_model_path', None)
+            if self.text_encoder_type == 'clip':
+                self.clip_model = self._try_load_clip(clip_version)
+            elif bert_model_path is not None:
+                self.clip_model = load_bert(bert_model_path, _native_lib=self._native_lib)
+            else:
+                self.clip_model = None
         self.output_process = OutputProcess(data_rep, self.input_feats, latent_dim, njoints, nfeats)
         # model/mdm.py:135; a plain attribute (no state-dict keys), the SMPL file is read at the first non-xyz call
         self.rot2xyz = Rotation2xyz(device="cpu", dataset=self.dataset, _native_lib=self._native_lib)
@@ -289,12 +297,18 @@ class MDM(nn.Module):
         return model
 
     def encode_text(self, raw_text):
-        """model/mdm.py:163-178 clip_encode_text (bert_encode_text :180-187 needs DistilBERT weights: cache instead)."""
+        """model/mdm.py:163-178 clip_encode_text, :180-187 bert_encode_text."""
         if self.text_encoder_type == 'bert':
-            if getattr(self, 'clip_model', None) is None:
-                raise RuntimeError("no DistilBERT attached (assign model.clip_model = load_bert(path), model/mdm.py:119): pass the "
+            bert = getattr(self, 'clip_model', None)
+            if bert is None:
+                raise RuntimeError("no DistilBERT attached: construct the model with bert_model_path=<local distilbert-base-uncased "
+                                   "directory> (or assign model.clip_model = mdm_amd.text_encoder.load_bert(path)), or pass the "
                                    "cached embedding as y['text_embed'] = (last_hidden_state [Ntok, B, 768], pad_mask [B, Ntok])")
-            enc_text, mask = self.clip_model(raw_text)        # model/mdm.py:180-187 bert_encode_text
+            if isinstance(bert, BERT):                        # the HIP encoder writes the decoder's token-major layout itself
+                input_ids, attention_mask = bert.tokenize(raw_text)
+                enc_text = bert.encode_ids(input_ids, attention_mask, token_major=True)
+                return enc_text, ~attention_mask.to(device=enc_text.device, dtype=torch.bool)
+            enc_text, mask = bert(raw_text)                   # a foreign module with the reference's interface
             return enc_text.permute(1, 0, 2), ~mask
         if getattr(self, 'clip_model', None) is None:
             raise RuntimeError("CLIP is not available in this environment: pass the cached embedding as "
