@@ -547,6 +547,67 @@ size_t mdm_text_workspace_bytes(const mdm_text_model_t* model, int32_t B, int32_
 int mdm_text_encode(const mdm_text_model_t* model, const int32_t* ids_dev, const int32_t* lens_dev, float* out_dev, int32_t B,
                     int32_t L, int32_t token_major, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The ST-GCN action recogniser of the UESTC evaluation (eval/a2m/stgcn_eval.py -> eval/a2m/recognition/models/stgcn.py, ten blocks,
+ * V = 24, 6 input channels) and of the unconstrained evaluation (eval/unconstrained/evaluate.py -> eval/unconstrained/models/stgcn.py,
+ * six blocks, V = 15, 3 input channels): eval mode, one person per sample, no length mask (the reference applies none), in exact fp32
+ * (additive to ABI 10; kernels: csrc/stgcn.h).  One entry point serves both networks: the network is a HOST array of block
+ * descriptors.  Every weight is a caller-owned, 16-byte aligned DEVICE array prepared once per model (mdm_amd/stgcn.py does it);
+ * "BN" below is BatchNorm2d in eval mode folded with the bias in front of it: scale = gamma / sqrt(var + eps),
+ * shift = (bias - mean) scale + beta, formed in fp64 and rounded once.
+ *
+ * One block (reference names under st_gcn_networks.N), with A_b = A * edge_importance[N] of shape [K][V][V] and c_in_p = c_in
+ * rounded up to a multiple of 4 (only the first block's c_in may need it; the pad columns of its weights are zero):
+ *   gcn_w   [c_out][K][c_in_p]     gcn.conv.weight [K c_out][c_in] with the k axis moved behind c_out (contraction index k c_in_p + ci)
+ *   gcn_scale [c_out]              tcn.0 (BN)
+ *   gcn_shift [V][c_out]           (sum_k gcn.conv.bias[k c_out + c] sum_v A_b[k][v][w] - mean[c]) scale[c] + beta[c]   per node w
+ *   nbr_idx [K][V][8] int32, nbr_w [K][V][8], nbr_cnt [K][V] int32
+ *                                  the non-zero A_b[k][v][w] of each (k, w): the v's in ascending order, their values, how many
+ *                                  (at most MDM_STGCN_MAX_NEIGHBOURS; idx < V; entries behind cnt are not read; a count or an index
+ *                                  outside its range is clamped into it)
+ *   tcn_w   [c_out][9][c_out]      tcn.2.weight [c_out][c_out][9][1] tap-major (contraction index tap c_out + c)
+ *   tcn_scale, tcn_shift [c_out]   tcn.3 (BN) with tcn.2.bias
+ *   residual                       MDM_STGCN_RES_NONE; _IDENTITY (c_in == c_out, stride 1: the block's input is added);
+ *                                  _CONV: res_w [c_out][c_in_p] (residual.0.weight), res_scale, res_shift [c_out] (residual.1 with
+ *                                  residual.0.bias)
+ * The block computes  y = relu(BN(gcn(x)));  out = relu(BN(conv9x1_stride(y)) + residual(x)),  T_out = (T - 1) / stride + 1. */
+#define MDM_STGCN_RES_NONE 0
+#define MDM_STGCN_RES_IDENTITY 1
+#define MDM_STGCN_RES_CONV 2
+#define MDM_STGCN_MAX_BLOCKS 16
+#define MDM_STGCN_MAX_NEIGHBOURS 8
+
+typedef struct mdm_stgcn_block {
+  const float* gcn_w; const float* gcn_scale; const float* gcn_shift;
+  const int32_t* nbr_idx; const float* nbr_w; const int32_t* nbr_cnt;
+  const float* tcn_w; const float* tcn_scale; const float* tcn_shift;
+  const float* res_w; const float* res_scale; const float* res_shift;   /* MDM_STGCN_RES_CONV only, else null */
+  int32_t c_in, c_out, stride, residual;
+} mdm_stgcn_block_t;
+
+/* blocks: a HOST array of n_blocks (1 .. MDM_STGCN_MAX_BLOCKS) descriptors; blocks[0].c_in is the input's channel count C (any
+ * positive number), every other c_in equals the c_out in front of it, every c_out is a positive multiple of 4 and the last one at
+ * most 1024; stride 1 .. 4.  V nodes (1 .. 64), K graph kernels (1 .. 8).  in_scale / in_shift [V C]: data_bn (BatchNorm1d over the
+ * V C channels, eval mode) as x scale + shift.  fcn_w [num_class][c_out of the last block], fcn_b [num_class]: the 1 x 1 `fcn`. */
+typedef struct mdm_stgcn_model {
+  const mdm_stgcn_block_t* blocks;
+  const float* in_scale; const float* in_shift;
+  const float* fcn_w; const float* fcn_b;
+  int32_t n_blocks, V, K, num_class;
+} mdm_stgcn_model_t;
+
+/* Bytes of workspace mdm_stgcn_forward needs for N samples of T frames; 0 on a bad argument (mdm_last_error says which).  In floats:
+ * three buffers of  max(N T V c_in_p of block 0, max over blocks of N T_b V c_out_b)  -- a block's input, the graph convolution's
+ * output and the block's output, T_b the block's INPUT frames -- plus 64 bytes. */
+size_t mdm_stgcn_workspace_bytes(const mdm_stgcn_model_t* model, int32_t N, int32_t T);
+
+/* x_dev [N, V, C, T] (the reference's batch["output"] / batch["x"]: T contiguous) -> features_dev [N, c_out of the last block], the
+ * mean over the last block's T' V positions, and yhat_dev [N, num_class], the logits.  A sample's results do not depend on N or on
+ * its row (bit for bit): one tile shape, one k order, fixed neighbour and pooling orders.  N >= 1, 1 <= T <= 65536, and
+ * N T V times the widest row below 2^31 (chunk the samples otherwise).  Launches: 1 + per block 2 (3 with a convolutional
+ * residual) + 1.  No device allocation, no synchronisation, every kernel on `stream`: capture-safe. */
+int mdm_stgcn_forward(const mdm_stgcn_model_t* model, const float* x_dev, float* features_dev, float* yhat_dev, int32_t N, int32_t T,
+                      void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = [
     "mdm_rot6d_to_smpl_joints", "mdm_smpl_workspace_bytes", "mdm_smpl_forward",
     "mdm_eval_workspace_bytes", "mdm_eval_motion_embeddings", "mdm_eval_text_embeddings",
     "mdm_text_workspace_bytes", "mdm_text_encode",
+    "mdm_stgcn_workspace_bytes", "mdm_stgcn_forward",
 ]
 # include/mdm_hip_probe.h: exported by the probe build only
 PROBE_SYMBOLS = ["mdm_debug_set", "mdm_debug_get", "mdm_linear_f16f6", "mdm_linear_f16f6_scratch_bytes", "mdm_probe_in_proj"]
@@ -79,6 +80,22 @@ class MdmTextModel(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("word_emb", "pos_emb", "emb_ln_g", "emb_ln_b")] + [("layers", C.POINTER(MdmTextLayer))] + \
                [(n, C.c_int32) for n in ("n_layers", "dim", "n_heads", "hidden", "vocab", "max_pos")] + [("ln_eps", C.c_float)]
 
+
+class MdmStgcnBlock(C.Structure):
+    """include/mdm_hip.h mdm_stgcn_block_t: one st_gcn block (graph convolution with its neighbour lists, temporal convolution, residual)."""
+    _fields_ = [(n, C.c_void_p) for n in ("gcn_w", "gcn_scale", "gcn_shift", "nbr_idx", "nbr_w", "nbr_cnt", "tcn_w", "tcn_scale",
+                                          "tcn_shift", "res_w", "res_scale", "res_shift")] + \
+               [(n, C.c_int32) for n in ("c_in", "c_out", "stride", "residual")]
+
+
+class MdmStgcnModel(C.Structure):
+    """include/mdm_hip.h mdm_stgcn_model_t."""
+    _fields_ = [("blocks", C.POINTER(MdmStgcnBlock))] + [(n, C.c_void_p) for n in ("in_scale", "in_shift", "fcn_w", "fcn_b")] + \
+               [(n, C.c_int32) for n in ("n_blocks", "V", "K", "num_class")]
+
+
+STGCN_RES = {"none": 0, "identity": 1, "conv": 2}      # MDM_STGCN_RES_*
+STGCN_MAX_BLOCKS, STGCN_MAX_NEIGHBOURS = 16, 8
 
 SMPL_POSE_REPS = {"rot6d": 0, "rotvec": 1, "rotmat": 2, "rotquat": 3}      # MDM_SMPL_*: feature counts 6, 3, 9, 4
 SMPL_REP_FEATS = {"rot6d": 6, "rotvec": 3, "rotmat": 9, "rotquat": 4}
@@ -165,6 +182,8 @@ class MdmLib:
             "mdm_eval_text_embeddings": (C.c_int, [P(MdmEvalModel), vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
             "mdm_text_workspace_bytes": (sz, [P(MdmTextModel), i32, i32]),
             "mdm_text_encode": (C.c_int, [P(MdmTextModel), vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+            "mdm_stgcn_workspace_bytes": (sz, [P(MdmStgcnModel), i32, i32]),
+            "mdm_stgcn_forward": (C.c_int, [P(MdmStgcnModel), vp, vp, vp, i32, i32, vp, sz, vp]),
         }
         probe_sig = {
             "mdm_debug_set": (C.c_int, [C.c_int, C.c_int]),
