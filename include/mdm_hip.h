@@ -145,6 +145,13 @@ void mdm_destroy(mdm_model_t* m);
  *                                 are bit-identical.  Taken on the sequence-tile route of the f16x3 mode for sequences of at most
  *                                 207 tokens; every other forward, and 0 (A/B and tests), runs one tile per sequence. */
 #define MDM_OPT_ENC_SHARED_LAYER0 7
+/*   MDM_OPT_ATTN_WIDE             1 (default): from 129 tokens on (five to seven 32-key tiles; up to 224) the split-precision self-attention
+ *                                 runs as ONE 8-wave workgroup per (sequence, head) -- a wave per query tile, the remaining waves copy
+ *                                 the K / V^T tiles into LDS for all of them -- instead of two 4-wave workgroups that each stream all of
+ *                                 K and V^T (csrc/attention_x3.h).  Same arithmetic in the same order: results are bit-identical.
+ *                                 0 (A/B and tests): the 4-wave kernel at every length.  MDM_OPT_ATTN_DIRECT_OUT = 1 selects the
+ *                                 4-wave kernel's direct form whatever this option says. */
+#define MDM_OPT_ATTN_WIDE 8
 int mdm_set_option(mdm_model_t* m, int32_t key, int32_t value);
 int mdm_get_option(const mdm_model_t* m, int32_t key, int32_t* value);
 

@@ -41,6 +41,14 @@ int mdm_linear_f16f6(const float* in_dev, const float* w_dev, const float* bias_
 int mdm_probe_in_proj(const float* tokens, const float* w, const float* bias, void* planes_dev, int32_t nseq, int32_t S,
                       int32_t D, void* scratch_dev, void* stream);
 
+/* mdm_attention_x3's contract (scratch included) with the choices it derives made by the caller: `lead` tokens in front of the
+ * frames are never masked (1 = trans_enc's condition token, 0 = trans_dec), wide = 1 / 0 the 8-wave / 4-wave form of
+ * csrc/attention_x3.h (MDM_OPT_ATTN_WIDE; the 8-wave form exists from 129 tokens on), and the output as fp32 rows (`out_dev`) and / or
+ * as hi / lo 16-bit planes [nseq * S][D] (`out_hi_dev`, `out_lo_dev`: both or neither).  The bit-identity tests of the two forms. */
+int mdm_probe_attention_x3(const float* qkv_dev, float* out_dev, void* out_hi_dev, void* out_lo_dev, const int32_t* lengths_dev,
+                           int32_t nseq, int32_t B, int32_t S, int32_t D, int32_t H, int32_t lead, int32_t wide, void* scratch_dev,
+                           size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,7 +76,9 @@ class Engine:
                                   context_len = 1 trans_dec model is the timestep embedding (model/mdm.py:256-257), not a prefix frame
           'enc_shared_layer0'     1 (default) = a guided trans_enc forward on the sequence-tile route computes layer 0's in_proj once
                                   per sample and writes the frame rows to both branches' planes (bit-identical results; sequences
-                                  of <= 207 tokens), 0 = one tile per sequence (A/B and tests)"""
+                                  of <= 207 tokens), 0 = one tile per sequence (A/B and tests)
+          'attn_wide'             1 (default) = self-attention over 129 .. 224 tokens as one 8-wave workgroup per (sequence, head)
+                                  with copy waves (bit-identical results), 0 = the 4-wave kernel at every length (A/B and tests)"""
         if name not in nat.OPTIONS:
             raise ValueError(f"unknown engine option {name!r}: one of {sorted(nat.OPTIONS)}")
         self.lib.check(self.lib.mdm_set_option(self.handle, nat.OPTIONS[name], int(value)), f"mdm_set_option({name})")

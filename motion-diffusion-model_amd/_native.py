@@ -31,11 +31,12 @@ EXPORTED_SYMBOLS = [
     "mdm_stgcn_workspace_bytes", "mdm_stgcn_forward",
 ]
 # include/mdm_hip_probe.h: exported by the probe build only
-PROBE_SYMBOLS = ["mdm_debug_set", "mdm_debug_get", "mdm_linear_f16f6", "mdm_linear_f16f6_scratch_bytes", "mdm_probe_in_proj"]
+PROBE_SYMBOLS = ["mdm_debug_set", "mdm_debug_get", "mdm_linear_f16f6", "mdm_linear_f16f6_scratch_bytes", "mdm_probe_in_proj",
+                 "mdm_probe_attention_x3"]
 ABI_VERSION = 10
 # include/mdm_hip.h MDM_OPT_*: per-handle run-time options (the library reads no environment variable)
 OPTIONS = {"small_gemm_max_seqs": 1, "small_gemm_row_tiles": 2, "dec_fused_xattn": 3, "dec_fused_selfattn": 4, "attn_direct_out": 5,
-           "dec_time_token": 6, "enc_shared_layer0": 7}
+           "dec_time_token": 6, "enc_shared_layer0": 7, "attn_wide": 8}
 ARCH = {"trans_enc": 0, "trans_dec": 1}
 
 
@@ -191,6 +192,7 @@ class MdmLib:
             "mdm_linear_f16f6_scratch_bytes": (sz, [i32, i32, i32]),
             "mdm_linear_f16f6": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
             "mdm_probe_in_proj": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+            "mdm_probe_attention_x3": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
         }
         self.has_probes = hasattr(lib, "mdm_debug_set")   # libmdm_hip_probe.so / the emulator build
         if self.has_probes:

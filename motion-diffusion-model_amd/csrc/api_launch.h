@@ -142,11 +142,24 @@ int launch_attention_x3_nkt(const QkvPlanes& qp, const int* lengths, int nseq, i
   }
 }
 
+// the WIDE form (attention_x3.h): one 8-wave workgroup per CU, one (sequence, head) per item, NKT 5 .. 7
+template <int NKT>
+int launch_attention_x3_wide_t(const QkvPlanes& qp, const int* lengths, int nseq, int B, int S, int D, float* out, p16_t* oh,
+                               p16_t* ol, hipStream_t s, int lead) {
+  auto k = &attention_x3_kernel_wide<NKT>;
+  const size_t lds = (size_t)axw_lds_bytes(NKT);
+  if (int rc = rt_allow_lds(k, lds)) return rc;
+  const int items = nseq * qp.H;
+  const int grid = std::min(items, x3_grid_limit());   // persistent: workgroup b takes items b, b + grid, ...
+  MDM_LAUNCH(k, dim3(grid), dim3(AXW_THREADS), lds, s, qp, lengths, S, D, B, lead, out, oh, ol, items);
+  return rt_launch_status();
+}
+
 // split-precision attention on the operand planes written by the in_proj epilogue (or qkv_pack_kernel)
 // `lead` tokens in front of the frames are never masked (trans_enc: the condition token; trans_dec: none -- its `lengths` count the
 // context_len prefix frames as frames)
 int launch_attention_x3(Profiler* pf, const QkvPlanes& qp, const int* lengths, int nseq, int B, int S, int D, float* out,
-                        p16_t* oh, p16_t* ol, hipStream_t s, int lead = 1, bool direct = false) {
+                        p16_t* oh, p16_t* ol, hipStream_t s, int lead = 1, bool direct = false, bool wide = true) {
   ProfScope ps(pf, MDM_PROF_ATTENTION, 4.0 * nseq * qp.H * (double)S * S * AX_HD, s);
   if (D != qp.H * AX_HD) return fail(MDM_EUNSUPPORTED, "attention: head_dim must be 128");
   if (S < 1) return fail(MDM_EUNSUPPORTED, "attention: no tokens");
@@ -158,6 +171,14 @@ int launch_attention_x3(Profiler* pf, const QkvPlanes& qp, const int* lengths, i
   }
   if (direct && out == nullptr && oh != nullptr)   // planes straight from the accumulators (attention_x3.h DIRECT)
     return launch_attention_x3_nkt<true>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
+  if (wide && qp.NKT >= 5) {   // S >= 129, where the 4-wave kernel runs two workgroups per item (MDM_OPT_ATTN_WIDE)
+    if (qp.NKT != (S + 31) / 32 || qp.SP != 32 * qp.NKT) return fail(MDM_EINVAL, "attention: the operand planes do not match the sequence length");
+    switch (qp.NKT) {
+      case 5: return launch_attention_x3_wide_t<5>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
+      case 6: return launch_attention_x3_wide_t<6>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
+      default: return launch_attention_x3_wide_t<7>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
+    }
+  }
   return launch_attention_x3_nkt<false>(qp, lengths, nseq, B, S, D, out, oh, ol, s, lead);
 }
 

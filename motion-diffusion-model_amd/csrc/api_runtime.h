@@ -162,6 +162,7 @@ struct mdm_model {
   bool fused_selfattn = true;               // ... and in_proj + self-attention of a (sequence, head) as one kernel (selfattn_block.h)
   bool enc_shared_l0 = true;                // MDM_OPT_ENC_SHARED_LAYER0: guided forwards compute layer 0's in_proj once per sample (gemm_x3.h PAIR)
   bool attn_direct = false;                 // attention_x3.h DIRECT: planes from the accumulators, next item's tiles 1, 2 in front of the stores
+  bool attn_wide = true;                    // attention_x3.h WIDE: one 8-wave workgroup per (sequence, head) with copy waves, from 129 tokens on
   X3Weights out_planes{nullptr, nullptr};  // poseFinal.weight, rows padded to jf_out (f16x3 OutputProcess)
   float* out_bias_pad = nullptr;            // poseFinal.bias padded to jf_out
   int jf_out = 0;                           // njoints*nfeats rounded up to a multiple of 4

@@ -15,7 +15,8 @@
 //                                        with 16-byte stores and (b) the probabilities, which come out of phase 1 in
 //                                        accumulator registers, are already the matching B operand.  Pad keys: finite.
 //
-// Two workgroups per (sequence, head); a wave owns 32 queries.  Everything is computed TRANSPOSED so the
+// Two 4-wave workgroups per (sequence, head) -- from five key tiles on ONE 8-wave workgroup with copy waves, the WIDE form
+// at the end of this file --; a wave owns 32 queries.  Everything is computed TRANSPOSED so the
 // softmax axis is lane-local (cdna_hip_programming.md T12's "swapped QK^T"):
 //   phase 1  St[key][query] = K . Q^T    A = K fragments (LDS, XOR-swizzled 256-byte rows, conflict-free b128 reads)
 //                                        B = this wave's Q fragments (registers, loaded once)
@@ -413,6 +414,319 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
 }
 
 inline size_t attention_x3_lds_bytes(int nkt) { return (size_t)ax_lds_bytes(nkt); }
+
+// WIDE form, NKT >= 5 (S >= 129: where the kernel above runs two workgroups per item).  512 threads = 8 waves, ONE persistent
+// workgroup per CU and one (sequence, head) per item, so K and V^T are streamed once per item instead of once per query half:
+//   * wave w < NKT owns query tile w and runs the per-tile body of the kernel above on the same fragments in the same order --
+//     every output bit is the same; it issues no LDS-DMA: its stream is fragment reads, MFMAs, softmax, Q loads and output;
+//   * waves w >= NKT are COPY waves without matrix work: they issue all 16 LDS-DMA pieces of every tile (dealt among two of
+//     them where there are several), retire them with a counted vmcnt and meet the compute waves at the per-tile barrier;
+//   * the ring has six 16 KB slots and the output staging LDS of its own (one 32 x AX_OST block per compute wave), so the
+//     stream runs on across item boundaries: the copy wave requests tile g + 3 of the workgroup's tile sequence right behind
+//     barrier g - 1 (the slot's last tenant, tile g - 3, was consumed before barrier g - 2) and keeps three tiles in flight
+//     behind the one it waits for (48 pieces of one copy wave: vmcnt has 6 bits);
+//   * a tile's ring slot is (tile index in the workgroup's sequence) % 6: a run-time term of the fragment addresses, one add per tile;
+//   * the output is staged per wave as above and leaves as 16-byte stores per plane (a lane takes 8 consecutive d).
+constexpr int AXW_RING = 6, AXW_AHEAD = 3, AXW_THREADS = 512;
+constexpr int AXW_STAGE = 32 * AX_OST * 4;    // bytes of output staging per compute wave
+constexpr int AXW_KMASK_OFF = AXW_RING * AX_SLOT, AXW_STAGE_OFF = AXW_KMASK_OFF + AX_KMASK_BYTES;
+constexpr int axw_lds_bytes(int nkt) { return AXW_STAGE_OFF + nkt * AXW_STAGE; }
+static_assert(axw_lds_bytes(7) <= 160 * 1024, "ring + mask + staging of seven compute waves fit the CU's LDS");
+__host__ __device__ __forceinline__ int axw_slot(int first, int t) {   // ring slot of tile t of an item whose tile 0 sits in `first`
+  const int s = first + t % AXW_RING;
+  return s >= AXW_RING ? s - AXW_RING : s;
+}
+
+template <int NKT>
+__global__ __launch_bounds__(AXW_THREADS) void attention_x3_kernel_wide(QkvPlanes P, const int* __restrict__ lengths, int S, int D,
+                                                                       int B, int lead, float* __restrict__ out,
+                                                                       p16_t* __restrict__ oh, p16_t* __restrict__ ol, int items) {
+  static_assert(NKT >= 5 && NKT <= 7, "one wave per query tile and at least one copy wave");
+  MDM_DYN_SMEM(unsigned char, lds);
+  constexpr int SP = 32 * NKT;
+  constexpr int NTILES = 2 * NKT;   // K tiles then V^T tiles
+  static_assert(NTILES > AXW_AHEAD, "the prologue's tiles belong to the first item");
+  constexpr int NCW = (8 - NKT) >= 2 ? 2 : 1;   // copy waves that carry pieces (a third one only keeps the barriers' count)
+  constexpr int PPW = 16 / NCW;                 // pieces per tile of such a wave
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+#ifdef MDM_EMU
+  const int w = tid >> 6;
+#else
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+#endif
+  const int H = P.H;
+  const int step = (int)gridDim.x;
+  int item = (int)blockIdx.x;   // the grid has at most `items` workgroups
+  int first = 0;                // ring slot of the current item's tile 0
+
+  if (w >= NKT) {
+    // ================= copy wave =================
+    const int c = w - NKT;
+    const bool carrier = c < NCW;
+    // the 16 KB tile format, source swizzles and pad-key clamp of the kernel above; this wave's pieces are PPW c .. PPW c + PPW - 1
+    auto issue_tile = [&](size_t sh, int t, int slot, int lv) {
+      if (!carrier) return;
+#pragma unroll
+      for (int i = 0; i < PPW; ++i) {
+        const int j = PPW * c + i, plane = j >> 3, idx = j & 7;
+        unsigned char* dst = lds + slot * AX_SLOT + plane * 8192 + idx * 1024;
+        if (t < NKT) {
+          const int key = 32 * t + 4 * idx + (lv >> 4);
+          const p16_t* src = (plane ? P.kl : P.kh) + (sh * SP + (size_t)min(key, S - 1)) * AX_HD + (((lv & 15) ^ (key & 15)) * 8);
+          glds16(src, dst);
+        } else {
+          const int d = 16 * idx + (lv >> 2);
+          const p16_t* src = (plane ? P.vl : P.vh) + ((sh * NKT + (size_t)(t - NKT)) * AX_HD + d) * 32 + (((lv & 3) ^ ((d >> 2) & 3)) * 8);
+          glds16(src, dst);
+        }
+      }
+    };
+#pragma unroll
+    for (int t = 0; t < AXW_AHEAD; ++t) issue_tile((size_t)item, t, t, lane);
+    for (;;) {
+      const int next = item + step;
+      const bool has_next = next < items;
+      const int first_next = axw_slot(first, NTILES);
+      // `lv` = the lane id, opaque per item: the per-lane source offsets are the same for every item, and hipcc otherwise hoists all of
+      // them out of the item loop and spills them (the kernel's register count is the larger of its two roles')
+      int lv = lane;
+#ifndef MDM_EMU
+      asm volatile("" : "+v"(lv));
+#endif
+      static_for<NTILES>([&](auto t_tag) __attribute__((always_inline)) {
+        constexpr int t = decltype(t_tag)::value;
+        constexpr int tn = t + AXW_AHEAD;
+        if constexpr (tn < NTILES) issue_tile((size_t)item, tn, axw_slot(first, tn), lv);
+        else if (has_next) issue_tile((size_t)next, tn - NTILES, axw_slot(first_next, tn - NTILES), lv);
+        // tile t landed?  LDS-DMA retires in order; behind it sit the tiles requested since (the stream ends with the last item)
+        constexpr int tail = (NTILES - 1 - t) < AXW_AHEAD ? (NTILES - 1 - t) : AXW_AHEAD;
+        if (has_next) ax_vm_wait<PPW * AXW_AHEAD>();
+        else ax_vm_wait<PPW * tail>();
+        wg_barrier();   // tile t visible to the compute waves; they are done with tile t - 1
+      });
+      if (!has_next) break;
+      item = next;
+      first = first_next;
+    }
+    wait_vmem_all();   // nothing of this workgroup may still be in flight towards its LDS when it is released
+    return;
+  }
+
+  // ================= compute wave: query tile w =================
+  const int r = lane & 31, h = lane >> 5;
+  const int qt = w;
+  const bool last_group = S > 32 * (NKT - 1) + 16;   // does the sequence reach into the last 16-key group?
+  p16x8 qh[8], ql[8];
+  auto load_q = [&](size_t sh) {
+    const size_t qo = (sh * SP + min(32 * qt + r, S - 1)) * AX_HD + 8 * h;   // pad queries: last real row
+#pragma unroll
+    for (int st = 0; st < 8; ++st) {
+      qh[st] = *reinterpret_cast<const p16x8*>(P.qh + qo + 16 * st);
+      ql[st] = *reinterpret_cast<const p16x8*>(P.ql + qo + 16 * st);
+    }
+  };
+  load_q((size_t)item);
+  const uint32_t klane = (uint32_t)(r * 256 + ((h ^ (r & 15)) * 16));
+  const uint32_t vlane = (uint32_t)(r * 64 + ((h ^ ((r >> 2) & 3)) * 16));
+#ifndef MDM_EMU
+  const uint32_t lbase = lds_addr_of(lds);
+#endif
+  float* const kmask = reinterpret_cast<float*>(lds + AXW_KMASK_OFF);
+  float* const so = reinterpret_cast<float*>(lds + AXW_STAGE_OFF) + w * (32 * AX_OST);   // wave-private
+
+  for (;;) {   // ---- one item = one (sequence, head)
+  const int seq = item / H, head = item - seq * H;
+  const int next = item + step;
+  const bool has_next = next < items;
+  int nvalid = S;
+  const uint32_t* kbits = nullptr;
+  if (lengths != nullptr) {
+    const int cnt = lengths[seq % B];
+    if (cnt >= 0) nvalid = min(S, lead + cnt);
+    else kbits = reinterpret_cast<const uint32_t*>(lengths + B + 8 * (seq % B));
+  }
+  if (tid < 32 * NKT) {
+    // additive key mask of this item (waves 0-3: all compute waves).  Read at the softmax, NKT barriers from here; whoever gets here has
+    // passed this workgroup's barrier of the previous item's last tile, which every wave reaches with its softmax behind it.
+    const int f = max(tid - lead, 0);
+    const bool ok = kbits == nullptr ? tid < nvalid : (tid < S && (tid < lead || ((kbits[f >> 5] >> (f & 31)) & 1u)));
+    kmask[tid] = ok ? 0.f : -INFINITY;
+  }
+
+#ifndef MDM_EMU
+  // the slot term stays a run-time scalar for every NKT (with twelve tiles `first` is provably 0, and hipcc then keeps the fragment
+  // addresses of all six slots in registers across the item: 6 VGPRs spilled at NKT = 6)
+  asm volatile("" : "+s"(first));
+#endif
+
+  f32x16 p[NKT];
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) p[kt][e] = 0.f;
+  f32x16 o[4];      // zeroed at the first V^T tile: must not be live (64 VGPRs) while the Q fragments are
+  float inv = 1.f;
+
+  static_for<NTILES>([&](auto t_tag) __attribute__((always_inline)) {
+    constexpr int t = decltype(t_tag)::value;
+    const uint32_t soff = (uint32_t)(axw_slot(first, t) * AX_SLOT);
+    wg_barrier();  // tile t visible (the copy waves waited for it); every wave is done with tile t-1
+    if constexpr (t == NTILES - 1) load_q(has_next ? (size_t)next : (size_t)item);   // unconditional, as above: dead after phase 1 on every path
+
+    if constexpr (t < NKT) {
+      // ---- phase 1, key tile t
+      {
+        p16x8 kh[3], kl[3];
+#ifdef MDM_EMU
+#define AX_RD_K(dst, plane, st) lds_read16(dst, lds, soff + (plane) * 8192 + (klane ^ ((st) << 5)))
+#else
+        const uint32_t kb = lbase + soff + klane;
+#define AX_RD_K(dst, plane, st) lds_read16<(plane) * 8192>(dst, kb ^ (uint32_t)((st) << 5))
+#endif
+        static_for<8 + 2>([&](auto u_tag) __attribute__((always_inline)) {
+          constexpr int u = decltype(u_tag)::value;
+          if constexpr (u < 8) {
+            AX_RD_K(kh[u % 3], 0, u);
+            AX_RD_K(kl[u % 3], 1, u);
+          }
+          if constexpr (u >= 2) {
+            constexpr int st = u - 2;
+            constexpr int younger = 2 * ((7 - st) < 2 ? (7 - st) : 2);
+            lds_wait<younger>(kh[st % 3], kl[st % 3]);
+            sched_fence();
+            p[t] = mfma_p16(kl[st % 3], qh[st], p[t]);
+            p[t] = mfma_p16(kh[st % 3], ql[st], p[t]);
+            p[t] = mfma_p16(kh[st % 3], qh[st], p[t]);
+            sched_fence();
+          }
+        });
+#undef AX_RD_K
+      }
+      if constexpr (t == NKT - 1) {
+        // ---- softmax over keys, exactly as above
+        float mx = -INFINITY;
+        {
+          const float* km = kmask + 4 * h;
+#pragma unroll
+          for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+              const float4 m4 = ld4(km + kt * 32 + 8 * g);
+              const float s0 = p[kt][4 * g] + m4.x, s1 = p[kt][4 * g + 1] + m4.y, s2 = p[kt][4 * g + 2] + m4.z,
+                          s3 = p[kt][4 * g + 3] + m4.w;
+              p[kt][4 * g] = s0; p[kt][4 * g + 1] = s1; p[kt][4 * g + 2] = s2; p[kt][4 * g + 3] = s3;
+              mx = fmaxf(mx, fmaxf(fmaxf(s0, s1), fmaxf(s2, s3)));
+            }
+        }
+        mx = fmaxf(mx, shfl_xor_f32(mx, 32));
+        mx -= 6.931471805599453f;   // probabilities as hi / lo of p * 2^10
+        float sum = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+#ifdef MDM_EMU
+            const float pe = expf(p[kt][e] - mx);
+#else
+            const float pe = __expf(p[kt][e] - mx);
+#endif
+            p[kt][e] = pe;
+            sum += pe;
+          }
+        sum += shfl_xor_f32(sum, 32);
+        inv = 1.0f / sum;
+      }
+    } else {
+      // ---- phase 2, key tile kt
+      constexpr int kt = t - NKT;
+      if constexpr (kt == 0) {
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) o[dt][e] = 0.f;
+      }
+      {
+        p16x8 vh[3], vl[3], ph, pl;
+#ifdef MDM_EMU
+#define AX_RD_V(dst, plane, s2, dt) lds_read16(dst, lds, soff + (plane) * 8192 + (dt) * 2048 + (vlane ^ ((s2) << 5)))
+#else
+        const uint32_t vb = lbase + soff + vlane;
+#define AX_RD_V(dst, plane, s2, dt) lds_read16<(plane) * 8192 + (dt) * 2048>(dst, vb ^ (uint32_t)((s2) << 5))
+#endif
+        static_for<8 + 2>([&](auto u_tag) __attribute__((always_inline)) {
+          constexpr int u = decltype(u_tag)::value;
+          if constexpr (u < 8) {
+            AX_RD_V(vh[u % 3], 0, u / 4, u % 4);
+            AX_RD_V(vl[u % 3], 1, u / 4, u % 4);
+          }
+          if constexpr (u >= 2) {
+            constexpr int uv = u - 2, s2 = uv / 4, dt = uv % 4;
+            if constexpr (dt == 0) {
+              float pv[8];
+#pragma unroll
+              for (int j = 0; j < 8; ++j) pv[j] = p[kt][8 * s2 + j];
+              split8(pv, ph, pl);
+            }
+            constexpr int younger = 2 * ((7 - uv) < 2 ? (7 - uv) : 2);
+            lds_wait<younger>(vh[uv % 3], vl[uv % 3]);
+            sched_fence();
+            if (kt < NKT - 1 || s2 == 0 || last_group) {   // a 16-key group wholly past the sequence: skipped, not multiplied
+              o[dt] = mfma_p16(vl[uv % 3], ph, o[dt]);
+              o[dt] = mfma_p16(vh[uv % 3], pl, o[dt]);
+              o[dt] = mfma_p16(vh[uv % 3], ph, o[dt]);
+            }
+            sched_fence();
+          }
+        });
+#undef AX_RD_V
+      }
+    }
+  });
+
+  // ---- stage this wave's O[32 queries][128 d] in two passes of 64 d (fp32, row stride AX_OST, wave-private LDS of its own: no
+  // rendezvous, the ring keeps streaming) and store coalesced, 8 consecutive d = 16 bytes per plane and lane
+  {
+    const size_t obase = (size_t)seq * S * D + head * AX_HD;
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+#pragma unroll
+      for (int dd = 0; dd < 2; ++dd)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int dt = 2 * pass + dd;
+          st4(&so[r * AX_OST + dd * 32 + 8 * g + 4 * h],
+              make_float4(o[dt][4 * g + 0] * inv, o[dt][4 * g + 1] * inv, o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv));
+        }
+      wave_lds_fence();
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = 8 * i + (lane >> 3), qq = 32 * qt + row, c8 = lane & 7;   // lane -> (row % 8, 8 consecutive d)
+        if (qq < S) {
+          const float4 v0 = ld4(&so[row * AX_OST + 8 * c8]), v1 = ld4(&so[row * AX_OST + 8 * c8 + 4]);
+          const size_t oo = obase + (size_t)qq * D + 64 * pass + 8 * c8;
+          if (out != nullptr) {
+            st4(out + oo, v0);
+            st4(out + oo + 4, v1);
+          }
+          if (oh != nullptr) {   // planes for the out_proj f16x3 GEMM
+            const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+            p16x8 hi, lo;
+            split8(v, hi, lo);
+            *reinterpret_cast<p16x8*>(oh + oo) = hi;
+            *reinterpret_cast<p16x8*>(ol + oo) = lo;
+          }
+        }
+      }
+      wave_lds_fence();
+    }
+  }
+  if (!has_next) break;
+  item = next;
+  first = axw_slot(first, NTILES);
+  }   // item loop
+}
 
 // Test / building-block helper: fp32 packed qkv [nseq*S][3D] (Q pre-scaled) -> the plane layouts above, pads zeroed.
 // One thread per (sequence, head, padded token, d); 2-byte scattered stores -- not a hot-path kernel (in the model the

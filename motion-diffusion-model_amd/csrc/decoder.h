@@ -257,7 +257,7 @@ struct DecStack {
       if (l != 0) { c.astat = y.sX; c.colsum = F.c_in; }
       if (int rc = launch_x3_ln(c, s)) return rc;
       if (int rc = launch_attention_x3(pf, ws.qp, len, share0 && l == 0 ? B : nseq, B, S, D, nullptr, ws.atth, ws.attl, s, /*lead=*/0,
-                                       m->attn_direct)) return rc;
+                                       m->attn_direct, m->attn_wide)) return rc;
     }
     X3Call c = LN(l == 0 ? X3K_OUT_PROJ_L0 : X3K_OUT_LN_RES, X3Operand{ws.atth, ws.attl}, P.out_proj, m->L(l, "self_attn.out_proj.bias"), M0, D, D);
     c.oh = y.Yh; c.ol = y.Yl; c.res = y.X(); c.ostat = y.sY;

@@ -119,7 +119,7 @@ int encoder(mdm_model* m, const Workspace& ws, int nseq, int B, int S, const int
         c.astat = ws.stat2; c.colsum = F.c_qkv; c.qp = &ws.qp; c.scale_cols = D; c.col_scale = qscale;
         if (int rc = launch_x3_ln(c, s)) return rc;
       }
-      if (int rc = launch_attention_x3(pf, ws.qp, lengths, nseq, B, S, D, nullptr, ws.atth, ws.attl, s, 1, m->attn_direct)) return rc;
+      if (int rc = launch_attention_x3(pf, ws.qp, lengths, nseq, B, S, D, nullptr, ws.atth, ws.attl, s, 1, m->attn_direct, m->attn_wide)) return rc;
       {  // xa = att.Wo + bo + layer input (normalised on the fly for l >= 1), + row statistics
         X3Call c = LN(l == 0 ? X3K_OUT_PROJ_L0 : X3K_OUT_LN_RES, attp, P.out_proj, m->L(l, "self_attn.out_proj.bias"), D, D);
         c.oh = ws.xah; c.ol = ws.xal; c.res = xb; c.ostat = ws.stat1;
@@ -146,7 +146,7 @@ int encoder(mdm_model* m, const Workspace& ws, int nseq, int B, int S, const int
     for (int l = 0; l < m->cfg.num_layers; ++l) {
       const mdm_model::LayerPlanes& P = m->planes[l];
       if (int rc = launch_in_proj_x3(pf, tokp, P.in_proj, m->L(l, "self_attn.in_proj_bias"), ws.qp, nseq, S, D, qscale, s)) return rc;
-      if (int rc = launch_attention_x3(pf, ws.qp, lengths, nseq, B, S, D, nullptr, ws.atth, ws.attl, s, 1, m->attn_direct)) return rc;
+      if (int rc = launch_attention_x3(pf, ws.qp, lengths, nseq, B, S, D, nullptr, ws.atth, ws.attl, s, 1, m->attn_direct, m->attn_wide)) return rc;
       // the residual stream lives as planes only (value = hi + lo): the GEMM writes the pre-norm sum as fp32, LayerNorm
       // turns it back into planes and does NOT write fp32 (one 103 MB stream less per LayerNorm)
       if (int rc = launch_linear_x3(pf, attp, P.out_proj, m->L(l, "self_attn.out_proj.bias"), nullptr, ws.tok, nullptr,

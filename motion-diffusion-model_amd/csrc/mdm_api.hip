@@ -158,6 +158,10 @@ int mdm_set_option(mdm_model_t* m, int32_t key, int32_t value) {
       if (value != 0 && value != 1) return fail(MDM_EINVAL, "mdm_set_option: MDM_OPT_ATTN_DIRECT_OUT must be 0 or 1");
       m->attn_direct = value != 0;
       return MDM_OK;
+    case MDM_OPT_ATTN_WIDE:
+      if (value != 0 && value != 1) return fail(MDM_EINVAL, "mdm_set_option: MDM_OPT_ATTN_WIDE must be 0 or 1");
+      m->attn_wide = value != 0;
+      return MDM_OK;
     case MDM_OPT_DEC_TIME_TOKEN:
       if (value != 0 && value != 1) return fail(MDM_EINVAL, "mdm_set_option: MDM_OPT_DEC_TIME_TOKEN must be 0 or 1");
       if (value == 1 && (m->cfg.arch != MDM_ARCH_TRANS_DEC || m->cfg.context_len != 1))
@@ -190,6 +194,7 @@ int mdm_get_option(const mdm_model_t* m, int32_t key, int32_t* value) {
     case MDM_OPT_DEC_FUSED_XATTN: *value = m->fused_xattn; return MDM_OK;
     case MDM_OPT_DEC_FUSED_SELFATTN: *value = m->fused_selfattn ? 1 : 0; return MDM_OK;
     case MDM_OPT_ATTN_DIRECT_OUT: *value = m->attn_direct ? 1 : 0; return MDM_OK;
+    case MDM_OPT_ATTN_WIDE: *value = m->attn_wide ? 1 : 0; return MDM_OK;
     case MDM_OPT_DEC_TIME_TOKEN: *value = m->dec_time_token ? 1 : 0; return MDM_OK;
     case MDM_OPT_ENC_SHARED_LAYER0: *value = m->enc_shared_l0 ? 1 : 0; return MDM_OK;
     default: return fail(MDM_EINVAL, "mdm_get_option: unknown key " + std::to_string(key));
@@ -764,6 +769,28 @@ int mdm_attention_x3(const float* qkv, float* out, const int32_t* lengths, int32
 }
 
 #ifdef MDM_PROBES
+// mdm_attention_x3 with the kernel form, the lead tokens and the outputs chosen by the caller: fp32 rows and / or hi, lo planes.
+// tests/test_*_attention_wide.py hold the wide form against the 4-wave kernel bit for bit.
+int mdm_probe_attention_x3(const float* qkv, float* out, void* out_hi, void* out_lo, const int32_t* lengths, int32_t nseq, int32_t B,
+                           int32_t S, int32_t D, int32_t H, int32_t lead, int32_t wide, void* scratch, size_t scratch_bytes,
+                           void* stream) {
+  ChainGuard chain_guard(stream);
+  if (!qkv || (!out && !out_hi) || (out_hi == nullptr) != (out_lo == nullptr) || !scratch || nseq <= 0 || B <= 0 || S <= 0 || H <= 0 ||
+      lead < 0)
+    return fail(MDM_EINVAL, "mdm_probe_attention_x3: bad argument");
+  if (D != H * AX_HD) return fail(MDM_EUNSUPPORTED, "attention: head_dim must be 128");
+  if (scratch_bytes < mdm_attention_x3_scratch_bytes(nseq, S, D)) return fail(MDM_ENOSPC, "mdm_probe_attention_x3: scratch too small");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int NKT = (S + 31) / 32, SP = 32 * NKT;
+  const size_t plane = (size_t)nseq * SP * D;
+  p16_t* q = static_cast<p16_t*>(scratch);
+  QkvPlanes qp{q, q + plane, q + 2 * plane, q + 3 * plane, q + 4 * plane, q + 5 * plane, SP, NKT, H};
+  MDM_LAUNCH(qkv_pack_kernel, dim3((int)std::min<size_t>((plane + 255) / 256, 4096)), dim3(256), 0, s, qkv, qp, nseq, S, D);
+  if (int rc = rt_launch_status()) return rc;
+  return launch_attention_x3(nullptr, qp, lengths, nseq, B, S, D, out, static_cast<p16_t*>(out_hi), static_cast<p16_t*>(out_lo), s, lead,
+                             /*direct=*/false, wide != 0);
+}
+
 // in_proj alone (the non-folded instantiation of layer 0): fp32 tokens [nseq * S][D] and in_proj weights [3D][D] -> the
 // attention operand planes, written to `planes_dev` (6 planes of nseq * SP * D 16-bit elements: qh ql kh kl vh vl).
 // `scratch_dev`: 4 * nseq * S * D + 12 * D * D bytes.  tools/in_proj_determinism.py compares repeated runs bit for bit.
