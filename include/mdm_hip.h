@@ -615,6 +615,43 @@ size_t mdm_stgcn_workspace_bytes(const mdm_stgcn_model_t* model, int32_t N, int3
 int mdm_stgcn_forward(const mdm_stgcn_model_t* model, const float* x_dev, float* features_dev, float* yhat_dev, int32_t N, int32_t T,
                       void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The HumanAct12 GRU action recogniser behind A2MEvaluation (eval/a2m/gru_eval.py -> eval/a2m/action2motion/models.py:6-61,
+ * MotionDiscriminator / MotionDiscriminatorForFID): nn.GRU(input_size, hidden_size, num_layers) over the frames, the last layer's
+ * output at frame lengths[b] - 1, features = tanh(linear1(.)), yhat = linear2(features); exact fp32 (additive to ABI 10; kernels:
+ * csrc/gru_recogniser.h).  Every weight is a caller-owned, 16-byte aligned DEVICE array in PyTorch's own layout:
+ *   layers[l].w_ih [3 H][I] (l = 0) or [3 H][H], w_hh [3 H][H], b_ih, b_hh [3 H]     recurrent.{weight,bias}_{ih,hh}_l<l>, gates r | z | n
+ *   lin1_w [mid][H], lin1_b [mid], lin2_w [num_class][mid], lin2_b [num_class]       linear1, linear2
+ * hidden_size 128 (the published checkpoint; 32 is built as the reduced width of the emulator tests), num_layers 1 .. 4, input_size
+ * any positive number (72 for HumanAct12, 54 for NTU-13), mid (30) and num_class 1 .. 64. */
+#define MDM_GRU_CLS_MAX_LAYERS 4
+
+typedef struct mdm_gru_cls_layer {
+  const float* w_ih; const float* w_hh; const float* b_ih; const float* b_hh;
+} mdm_gru_cls_layer_t;
+
+typedef struct mdm_gru_cls_model {
+  mdm_gru_cls_layer_t layers[MDM_GRU_CLS_MAX_LAYERS];      /* the first num_layers are read */
+  const float* lin1_w; const float* lin1_b; const float* lin2_w; const float* lin2_b;
+  int32_t input_size, hidden_size, num_layers, mid, num_class;
+} mdm_gru_cls_model_t;
+
+/* Bytes of workspace mdm_gru_cls_forward needs for B sequences of T frames; 0 on a bad argument (mdm_last_error says which).  In
+ * floats: B T 3 H (a layer's input projections) + B T H (a layer's outputs; only with num_layers > 1) + B H, plus 64 bytes. */
+size_t mdm_gru_cls_workspace_bytes(const mdm_gru_cls_model_t* model, int32_t B, int32_t T);
+
+/* x_dev [B, I, T] (the reference's [bs, njoints, nfeats, T]: T contiguous), lens_dev int32 [B], h0_dev [num_layers, B, H] (the
+ * reference's `hidden_unit`) -> features_dev [B, mid] (what MotionDiscriminatorForFID returns) and yhat_dev [B, num_class] (what
+ * MotionDiscriminator returns).  lens_dev is read on the device and clamped to [1, T] (the reference wraps a zero length to the
+ * last frame and fails beyond T); frames behind a row's length are not read.  A row's results do not depend on B, on its position
+ * or on the other rows' lengths (bit for bit).  Refused with a message: a null pointer; a weight that is not 16-byte aligned or an
+ * x_dev / lens_dev / h0_dev / features_dev / yhat_dev that is not 4-byte aligned; B or T < 1; a hidden_size without an
+ * instantiation; num_layers outside 1 .. 4; a workspace below mdm_gru_cls_workspace_bytes; B T 3 H >= 2^31 (chunk the rows).
+ * Launches: per layer one GEMM and ONE recurrence kernel (all T steps; no cross-workgroup synchronisation), + 1.  Joins the
+ * one-chain-per-device guard (CONCURRENCY).  No device allocation, no synchronisation, every kernel on `stream`: capture-safe. */
+int mdm_gru_cls_forward(const mdm_gru_cls_model_t* model, const float* x_dev, const int32_t* lens_dev, const float* h0_dev,
+                        float* features_dev, float* yhat_dev, int32_t B, int32_t T, void* workspace_dev, size_t workspace_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = [
     "mdm_eval_workspace_bytes", "mdm_eval_motion_embeddings", "mdm_eval_text_embeddings",
     "mdm_text_workspace_bytes", "mdm_text_encode",
     "mdm_stgcn_workspace_bytes", "mdm_stgcn_forward",
+    "mdm_gru_cls_workspace_bytes", "mdm_gru_cls_forward",
 ]
 # include/mdm_hip_probe.h: exported by the probe build only
 PROBE_SYMBOLS = ["mdm_debug_set", "mdm_debug_get", "mdm_linear_f16f6", "mdm_linear_f16f6_scratch_bytes", "mdm_probe_in_proj",
@@ -93,6 +94,20 @@ class MdmStgcnModel(C.Structure):
     """include/mdm_hip.h mdm_stgcn_model_t."""
     _fields_ = [("blocks", C.POINTER(MdmStgcnBlock))] + [(n, C.c_void_p) for n in ("in_scale", "in_shift", "fcn_w", "fcn_b")] + \
                [(n, C.c_int32) for n in ("n_blocks", "V", "K", "num_class")]
+
+
+class MdmGruClsLayer(C.Structure):
+    """include/mdm_hip.h mdm_gru_cls_layer_t: one nn.GRU layer in PyTorch's layouts (gates r | z | n)."""
+    _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh")]
+
+
+GRU_CLS_MAX_LAYERS = 4      # MDM_GRU_CLS_MAX_LAYERS
+
+
+class MdmGruClsModel(C.Structure):
+    """include/mdm_hip.h mdm_gru_cls_model_t."""
+    _fields_ = [("layers", MdmGruClsLayer * GRU_CLS_MAX_LAYERS)] + [(n, C.c_void_p) for n in ("lin1_w", "lin1_b", "lin2_w", "lin2_b")] + \
+               [(n, C.c_int32) for n in ("input_size", "hidden_size", "num_layers", "mid", "num_class")]
 
 
 STGCN_RES = {"none": 0, "identity": 1, "conv": 2}      # MDM_STGCN_RES_*
@@ -185,6 +200,8 @@ class MdmLib:
             "mdm_text_encode": (C.c_int, [P(MdmTextModel), vp, vp, vp, i32, i32, i32, vp, sz, vp]),
             "mdm_stgcn_workspace_bytes": (sz, [P(MdmStgcnModel), i32, i32]),
             "mdm_stgcn_forward": (C.c_int, [P(MdmStgcnModel), vp, vp, vp, i32, i32, vp, sz, vp]),
+            "mdm_gru_cls_workspace_bytes": (sz, [P(MdmGruClsModel), i32, i32]),
+            "mdm_gru_cls_forward": (C.c_int, [P(MdmGruClsModel), vp, vp, vp, vp, vp, i32, i32, vp, sz, vp]),
         }
         probe_sig = {
             "mdm_debug_set": (C.c_int, [C.c_int, C.c_int]),

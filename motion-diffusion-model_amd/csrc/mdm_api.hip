@@ -36,6 +36,7 @@
 #include "evaluator.h"
 #include "text_encoder.h"
 #include "stgcn.h"
+#include "gru_recogniser.h"
 
 using namespace mdm;
 
@@ -1434,3 +1435,5 @@ int mdm_stgcn_forward(const mdm_stgcn_model_t* m, const float* x, float* feature
 }
 
 }  // extern "C"
+
+#include "gru_recogniser_api.h"
