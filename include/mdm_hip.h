@@ -652,6 +652,54 @@ int mdm_gru_cls_forward(const mdm_gru_cls_model_t* model, const float* x_dev, co
                         float* features_dev, float* yhat_dev, int32_t B, int32_t T, void* workspace_dev, size_t workspace_bytes,
                         void* stream);
 
+/* The text tower of OpenAI CLIP (clip/model.py CLIP.encode_text; ViT-B/32 conditions the `text_encoder_type='clip'` checkpoints):
+ * token ids -> text_embed, in exact fp32 (additive to ABI 10; kernels: csrc/clip_text.h, csrc/text_encoder.h).
+ *   x = tok_emb[id] + pos_emb[t];  per layer (pre-LN, eps 1e-5): x += out(attn(ln_1(x))), causal (query t sees the keys t' <= t),
+ *   heads of 64, scores / 8;  x += proj(quick_gelu(fc(ln_2(x)))), quick_gelu(v) = v sigmoid(1.702 v);
+ *   out[b] = ln_final(x[b, lens[b] - 1]) text_proj^T, lens[b] - 1 being the prompt's EOT (upstream: argmax of the ids).
+ * Every weight is a caller-owned, 16-byte aligned fp32 DEVICE array, prepared once per model (mdm_amd/clip_text.py does it).
+ *
+ * One layer (OpenAI names under transformer.resblocks.N):
+ *   ln1_g, ln1_b [dim]                    ln_1                       ln2_g, ln2_b [dim]         ln_2
+ *   qkv_w [3 dim][dim], qkv_b [3 dim]     attn.in_proj_weight / in_proj_bias, the q rows (weight AND bias) already multiplied by 1/8
+ *   out_w [dim][dim], out_b [dim]         attn.out_proj
+ *   fc_w [mlp][dim], fc_b [mlp]           mlp.c_fc                   proj_w [dim][mlp], proj_b [dim]   mlp.c_proj */
+typedef struct mdm_clip_text_layer {
+  const float* ln1_g; const float* ln1_b;
+  const float* qkv_w; const float* qkv_b;
+  const float* out_w; const float* out_b;
+  const float* ln2_g; const float* ln2_b;
+  const float* fc_w; const float* fc_b;
+  const float* proj_w; const float* proj_b;
+} mdm_clip_text_layer_t;
+
+/* tok_emb [vocab][dim], pos_emb [max_pos][dim]: token_embedding.weight, positional_embedding.  lnf_g / lnf_b [dim]: ln_final.
+ * text_proj [embed][dim]: text_projection TRANSPOSED (upstream keeps [dim][embed]).  layers: a HOST array of n_layers structs.
+ * dim == 64 n_heads and dim <= 1024; mlp and embed positive multiples of 4; 1 <= n_layers <= 32; vocab >= 1; max_pos >= 1. */
+typedef struct mdm_clip_text_model {
+  const float* tok_emb; const float* pos_emb;
+  const float* lnf_g; const float* lnf_b;
+  const float* text_proj;
+  const mdm_clip_text_layer_t* layers;
+  int32_t n_layers, dim, n_heads, mlp, vocab, max_pos, embed;
+} mdm_clip_text_model_t;
+
+/* Bytes of workspace mdm_clip_text_encode needs for B prompts padded to L tokens; 0 on a bad argument (mdm_last_error says which).
+ * In floats: B L (6 dim + mlp) + B dim  -- the residual rows, their LayerNorm, q | k | v, the attention output, the mlp's hidden rows
+ * and the normalised EOT rows -- plus 64 bytes. */
+size_t mdm_clip_text_workspace_bytes(const mdm_clip_text_model_t* model, int32_t B, int32_t L);
+
+/* ids_dev [B, L] int32, lens_dev [B] int32 (tokens per prompt up to and including its EOT) -> out_dev [B, embed].  The ids behind a
+ * length are not read, and a prompt's row does not depend on L, on B or on the other prompts (bit for bit); pass L = max(lens),
+ * not the tokenizer's context length.  1 <= L <= min(128, max_pos).  lens[b] in [1, L] and ids < vocab are the caller's duty (a
+ * host tokenizer made them; an id outside the table is clamped into it, a length outside [1, L] likewise).  Refused with a message:
+ * a null model or pointer, a weight or out_dev that is not 16-byte aligned (named), dim != 64 n_heads, dim > 1024, L > max_pos,
+ * B L times the widest row >= 2^31 (chunk the prompts), a workspace below mdm_clip_text_workspace_bytes.
+ * Launches: one for the embedding, 7 per layer, two for ln_final over the EOT rows and the projection.  Joins the
+ * one-chain-per-device guard (CONCURRENCY).  No device allocation, no synchronisation, every kernel on `stream`: capture-safe. */
+int mdm_clip_text_encode(const mdm_clip_text_model_t* model, const int32_t* ids_dev, const int32_t* lens_dev, float* out_dev,
+                         int32_t B, int32_t L, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

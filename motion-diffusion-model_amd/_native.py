@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "mdm_text_workspace_bytes", "mdm_text_encode",
     "mdm_stgcn_workspace_bytes", "mdm_stgcn_forward",
     "mdm_gru_cls_workspace_bytes", "mdm_gru_cls_forward",
+    "mdm_clip_text_workspace_bytes", "mdm_clip_text_encode",
 ]
 # include/mdm_hip_probe.h: exported by the probe build only
 PROBE_SYMBOLS = ["mdm_debug_set", "mdm_debug_get", "mdm_linear_f16f6", "mdm_linear_f16f6_scratch_bytes", "mdm_probe_in_proj",
@@ -108,6 +109,18 @@ class MdmGruClsModel(C.Structure):
     """include/mdm_hip.h mdm_gru_cls_model_t."""
     _fields_ = [("layers", MdmGruClsLayer * GRU_CLS_MAX_LAYERS)] + [(n, C.c_void_p) for n in ("lin1_w", "lin1_b", "lin2_w", "lin2_b")] + \
                [(n, C.c_int32) for n in ("input_size", "hidden_size", "num_layers", "mid", "num_class")]
+
+
+class MdmClipTextLayer(C.Structure):
+    """include/mdm_hip.h mdm_clip_text_layer_t: one residual block of CLIP's text tower (in_proj stacked q | k | v, the q rows pre-scaled by 1/8)."""
+    _fields_ = [(n, C.c_void_p) for n in ("ln1_g", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_g", "ln2_b", "fc_w", "fc_b", "proj_w",
+                                          "proj_b")]
+
+
+class MdmClipTextModel(C.Structure):
+    """include/mdm_hip.h mdm_clip_text_model_t."""
+    _fields_ = [(n, C.c_void_p) for n in ("tok_emb", "pos_emb", "lnf_g", "lnf_b", "text_proj")] + [("layers", C.POINTER(MdmClipTextLayer))] + \
+               [(n, C.c_int32) for n in ("n_layers", "dim", "n_heads", "mlp", "vocab", "max_pos", "embed")]
 
 
 STGCN_RES = {"none": 0, "identity": 1, "conv": 2}      # MDM_STGCN_RES_*
@@ -198,6 +211,8 @@ class MdmLib:
             "mdm_eval_text_embeddings": (C.c_int, [P(MdmEvalModel), vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
             "mdm_text_workspace_bytes": (sz, [P(MdmTextModel), i32, i32]),
             "mdm_text_encode": (C.c_int, [P(MdmTextModel), vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+            "mdm_clip_text_workspace_bytes": (sz, [P(MdmClipTextModel), i32, i32]),
+            "mdm_clip_text_encode": (C.c_int, [P(MdmClipTextModel), vp, vp, vp, i32, i32, vp, sz, vp]),
             "mdm_stgcn_workspace_bytes": (sz, [P(MdmStgcnModel), i32, i32]),
             "mdm_stgcn_forward": (C.c_int, [P(MdmStgcnModel), vp, vp, vp, i32, i32, vp, sz, vp]),
             "mdm_gru_cls_workspace_bytes": (sz, [P(MdmGruClsModel), i32, i32]),

@@ -574,6 +574,8 @@ template <int N> __device__ __forceinline__ void wait_vmem_upto() {   // vmcnt(N
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
+// x sigmoid(a x): SiLU at a = 1 (1.0f * x is x: silu's bits) and clip/model.py's QuickGELU at a = 1.702, on one copy of the code
+__device__ __forceinline__ float sigmoid_gate(float x, float a) { return x / (1.0f + expf(-(a * x))); }
 
 // XCD-aware bijective remap of a linear workgroup id (cdna_hip_programming.md T1): hardware places
 // block b on XCD b%8; give each XCD a contiguous chunk of logical tiles so neighbours share its L2.

@@ -161,7 +161,7 @@ struct CfgTokenLoader {
 // the index arithmetic (divisions by T, base offsets) is not repeated 64 times.  Lanes 0..31 of a wave
 // hold 32 consecutive n for a fixed m, so n-contiguous destinations are written in 128-byte runs.
 // ------------------------------------------------------------------------------------------------
-enum { ACT_NONE = 0, ACT_GELU = 1, ACT_SILU = 2 };
+enum { ACT_NONE = 0, ACT_GELU = 1, ACT_SILU = 2, ACT_QGELU = 3 };   // QGELU (CLIP's text tower): LinearEpilogue only, on SILU's code
 
 // v = act(acc + bias[n]) * (n < scale_cols ? col_scale : 1) + (res ? res[m][n] : 0);
 // out[m][n] = v (if out) and/or the 16-bit split planes oh/ol[m][n] = hi/lo(v) (if oh) for a following f16x3 GEMM.
@@ -188,7 +188,7 @@ struct LinearEpilogue {
   __device__ __forceinline__ void store(const Row& r, const Col& c, float acc, float resv) const {
     float v = acc + c.bias;
     if (act == ACT_GELU) v = gelu_erf(v);
-    else if (act == ACT_SILU) v = silu(v);
+    else if (act >= ACT_SILU) v = sigmoid_gate(v, act == ACT_QGELU ? 1.702f : 1.0f);
     v *= c.mult;
     const size_t o = r.base + c.n;
     v += resv;
@@ -205,7 +205,7 @@ struct LinearEpilogue {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       if (act == ACT_GELU) v[q] = gelu_erf(v[q]);
-      else if (act == ACT_SILU) v[q] = silu(v[q]);
+      else if (act >= ACT_SILU) v[q] = sigmoid_gate(v[q], act == ACT_QGELU ? 1.702f : 1.0f);
       if (n + q < scale_cols) v[q] *= col_scale;
       v[q] += rr[q];
     }

@@ -35,6 +35,7 @@
 #include "smpl_mesh.h"
 #include "evaluator.h"
 #include "text_encoder.h"
+#include "clip_text.h"
 #include "stgcn.h"
 #include "gru_recogniser.h"
 
@@ -1281,7 +1282,7 @@ int mdm_text_encode(const mdm_text_model_t* m, const int32_t* ids, const int32_t
   if (int rc = text_ln(ln, s)) return rc;
   ln.ids = nullptr;
   ln.in = x;
-  auto attn_k = &text_attn_kernel;
+  auto attn_k = &text_attn_kernel<false>;
   const int nqt = (L + 31) / 32;
   for (int l = 0; l < m->n_layers; ++l) {
     const mdm_text_layer_t& y = m->layers[l];
@@ -1298,6 +1299,101 @@ int mdm_text_encode(const mdm_text_model_t* m, const int32_t* ids, const int32_t
     if (int rc = text_ln(ln, s)) return rc;
   }
   return MDM_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Validation shared by mdm_clip_text_workspace_bytes and mdm_clip_text_encode; 0 or a negative code with the message set (it names the field)
+int clip_text_plan(const char* fn, const mdm_clip_text_model_t* m, int B, int L, size_t& floats) {
+  const std::string f = std::string(fn) + ": ";
+  if (m == nullptr) return fail(MDM_EINVAL, f + "null model");
+  if (B < 1) return fail(MDM_EINVAL, f + "B must be at least 1");
+  if (L < 1) return fail(MDM_EINVAL, f + "L must be at least 1 token");
+  if (L > TXT_MAX_L) return fail(MDM_EUNSUPPORTED, f + "L must be at most 128 tokens (the attention kernel keeps 4 key tiles of 32)");
+  if (m->max_pos < 1) return fail(MDM_EINVAL, f + "max_pos must be at least 1");
+  if (L > m->max_pos) return fail(MDM_EINVAL, f + "L exceeds max_pos, the rows of the position table (" + std::to_string(m->max_pos) + ")");
+  if (m->n_heads < 1 || m->dim != TXT_HD * m->n_heads) return fail(MDM_EUNSUPPORTED, f + "dim must equal 64 * n_heads (heads of 64)");
+  if (m->dim > TXT_MAX_DIM) return fail(MDM_EUNSUPPORTED, f + "dim must be at most 1024 (the LayerNorm rows)");
+  if (m->mlp < 4 || m->mlp % 4 != 0) return fail(MDM_EUNSUPPORTED, f + "mlp must be a positive multiple of 4");
+  if (m->embed < 4 || m->embed % 4 != 0) return fail(MDM_EUNSUPPORTED, f + "embed must be a positive multiple of 4");
+  if (m->n_layers < 1 || m->n_layers > 32) return fail(MDM_EUNSUPPORTED, f + "n_layers must be between 1 and 32");
+  if (m->vocab < 1) return fail(MDM_EINVAL, f + "vocab must be at least 1");
+  auto check = [&](const float* q, const std::string& name) {
+    if (q == nullptr) return fail(MDM_EINVAL, f + "null weight pointer " + name);
+    if ((reinterpret_cast<uintptr_t>(q) & 15) != 0) return fail(MDM_EINVAL, f + "weight pointer " + name + " must be 16-byte aligned");
+    return 0;
+  };
+  const float* top[] = {m->tok_emb, m->pos_emb, m->lnf_g, m->lnf_b, m->text_proj};
+  const char* top_names[] = {"tok_emb", "pos_emb", "lnf_g", "lnf_b", "text_proj"};
+  for (int i = 0; i < 5; ++i)
+    if (int rc = check(top[i], top_names[i])) return rc;
+  if (m->layers == nullptr) return fail(MDM_EINVAL, f + "null layers");
+  static const char* layer_names[] = {"ln1_g", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_g", "ln2_b", "fc_w", "fc_b", "proj_w", "proj_b"};
+  for (int l = 0; l < m->n_layers; ++l) {
+    const mdm_clip_text_layer_t& y = m->layers[l];
+    const float* ptrs[] = {y.ln1_g, y.ln1_b, y.qkv_w, y.qkv_b, y.out_w, y.out_b, y.ln2_g, y.ln2_b, y.fc_w, y.fc_b, y.proj_w, y.proj_b};
+    for (int i = 0; i < 12; ++i)
+      if (int rc = check(ptrs[i], "layers[" + std::to_string(l) + "]." + layer_names[i])) return rc;
+  }
+  // (row counts and offsets inside the GEMMs are 32-bit)
+  if ((int64_t)B * L * std::max<int64_t>(3 * (int64_t)m->dim, m->mlp) >= (1ll << 31) || (int64_t)B * m->embed >= (1ll << 31))
+    return fail(MDM_EUNSUPPORTED, f + "B too large for one call: chunk the prompts (a row's result does not depend on the batch)");
+  floats = (size_t)B * L * (6 * (size_t)m->dim + m->mlp) + (size_t)B * m->dim;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mdm_clip_text_workspace_bytes(const mdm_clip_text_model_t* model, int32_t B, int32_t L) {
+  size_t floats = 0;
+  if (clip_text_plan("mdm_clip_text_workspace_bytes", model, B, L, floats) != 0) return 0;
+  return floats * sizeof(float) + 64;
+}
+
+int mdm_clip_text_encode(const mdm_clip_text_model_t* m, const int32_t* ids, const int32_t* lens, float* out, int32_t B, int32_t L,
+                         void* ws, size_t ws_bytes, void* stream) {
+  size_t floats = 0;
+  if (int rc = clip_text_plan("mdm_clip_text_encode", m, B, L, floats)) return rc;
+  if (!ids || !lens || !out || !ws) return fail(MDM_EINVAL, "mdm_clip_text_encode: null ids_dev, lens_dev, out_dev or workspace_dev");
+  if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) return fail(MDM_EINVAL, "mdm_clip_text_encode: out_dev must be 16-byte aligned");
+  if (ws_bytes < floats * sizeof(float) + 64) return fail(MDM_ENOSPC, "mdm_clip_text_encode: workspace_bytes too small (mdm_clip_text_workspace_bytes)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ChainGuard chain_guard(stream);
+  const int D = m->dim, H = m->n_heads, FF = m->mlp, M = B * L;
+  float* x = eval_ws(ws);                      // [M][D] the residual stream
+  float* xn = x + (size_t)M * D;               // [M][D] ln_1(x) / ln_2(x)
+  float* qkv = xn + (size_t)M * D;             // [M][3D]
+  float* ctx = qkv + (size_t)M * 3 * D;        // [M][D]
+  float* ffn = ctx + (size_t)M * D;            // [M][FF]
+  float* eot = ffn + (size_t)M * FF;           // [B][D] ln_final of the EOT rows
+  auto embed_k = &clip_embed_kernel;
+  MDM_LAUNCH(embed_k, dim3((unsigned)((M * (D / 4) + 255) / 256)), dim3(256), 0, s, ids, lens, m->tok_emb, m->pos_emb, x, (int)B, (int)L, D,
+             (int)m->vocab);
+  if (int rc = rt_launch_status()) return rc;
+  TextLnArgs ln{x, nullptr, nullptr, nullptr, nullptr, nullptr, lens, xn, B, L, D, 0, CLIP_LN_EPS, 0};
+  auto attn_k = &text_attn_kernel<true>;
+  const int nqt = (L + 31) / 32;
+  for (int l = 0; l < m->n_layers; ++l) {
+    const mdm_clip_text_layer_t& y = m->layers[l];
+    ln.gamma = y.ln1_g; ln.beta = y.ln1_b;
+    if (int rc = text_ln(ln, s)) return rc;
+    if (int rc = text_linear(xn, y.qkv_w, y.qkv_b, nullptr, qkv, M, 3 * D, D, ACT_NONE, s)) return rc;
+    MDM_LAUNCH(attn_k, dim3((unsigned)(B * H * nqt)), dim3(64), text_attn_lds_bytes(L), s, (const float*)qkv, lens, ctx, (int)L, D, H);
+    if (int rc = rt_launch_status()) return rc;
+    if (int rc = text_linear(ctx, y.out_w, y.out_b, x, x, M, D, D, ACT_NONE, s)) return rc;      // + x, in place
+    ln.gamma = y.ln2_g; ln.beta = y.ln2_b;
+    if (int rc = text_ln(ln, s)) return rc;
+    if (int rc = text_linear(xn, y.fc_w, y.fc_b, nullptr, ffn, M, FF, D, ACT_QGELU, s)) return rc;
+    if (int rc = text_linear(ffn, y.proj_w, y.proj_b, x, x, M, D, FF, ACT_NONE, s)) return rc;   // + x, in place
+  }
+  auto eot_k = &clip_eot_ln_kernel;
+  MDM_LAUNCH(eot_k, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, (const float*)x, lens, m->lnf_g, m->lnf_b, eot, (int)B, (int)L, D);
+  if (int rc = rt_launch_status()) return rc;
+  return text_linear(eot, m->text_proj, nullptr, nullptr, out, B, m->embed, D, ACT_NONE, s);
 }
 
 }  // extern "C"

@@ -26,6 +26,9 @@ inline size_t text_attn_lds_bytes(int L) { return (size_t)((L + 31) / 32) * 32 *
 // cross-half exchange, and the probabilities feed Ot[d][query] = V^T . P^T from the registers they are in.  K, then V, then the
 // output tile share the LDS buffer.  Key tiles: nkt = ceil(len / 32) of this sequence; keys len .. 32 nkt - 1 are zero-filled in
 // LDS and get p = 0 exactly; the sums over keys run tile by tile, register by register, in that one order.
+// CAUSAL (clip_text.h): query t sees the keys t' <= t only, so query tile qt runs the key tiles 0 .. qt and masks the diagonal one
+// per element; a row's sums still run over its own key tiles in the one order, whatever the tiles behind them hold.
+template <bool CAUSAL>
 __global__ __launch_bounds__(64) void text_attn_kernel(const float* __restrict__ qkv, const int* __restrict__ lens,
                                                        float* __restrict__ ctx, int L, int D, int H) {
   MDM_DYN_SMEM(float, smem);             // ceil(L / 32) * 32 rows x TXT_KLD floats
@@ -46,7 +49,7 @@ __global__ __launch_bounds__(64) void text_attn_kernel(const float* __restrict__
     for (int idx = lane; idx < nq * 16; idx += 64) st4(obase + (size_t)(idx >> 4) * D + 4 * (idx & 15), zero4());
     return;
   }
-  const int nkt = (len + 31) / 32;
+  const int nkt = CAUSAL ? qt + 1 : (len + 31) / 32;      // (q0 < len here, so tile qt holds keys)
 
   // ---- Q fragment: query row q0 + r, this lane-half's 32 d's
   float qf[32];
@@ -91,7 +94,8 @@ __global__ __launch_bounds__(64) void text_attn_kernel(const float* __restrict__
   for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const float s = (kt * 32 + mfma_row(e, h) < len) ? p[kt][e] : -INFINITY;
+      const int key = kt * 32 + mfma_row(e, h);
+      const float s = (key < len && (!CAUSAL || key <= q0 + r)) ? p[kt][e] : -INFINITY;
       p[kt][e] = s;
       mx = fmaxf(mx, s);
     }

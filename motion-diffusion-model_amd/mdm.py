@@ -23,6 +23,7 @@ from . import _native as nat
 from . import _engine
 from ._engine import Engine
 from .rotation2xyz import Rotation2xyz
+from .clip_text import ClipText, load_clip_text
 from .text_encoder import BERT, load_bert
 
 
@@ -270,8 +271,12 @@ class MDM(nn.Module):
             self.embed_text = nn.Linear(clip_dim, latent_dim)
             # CLIP is outside the hot path (callers cache y['text_embed']); DistilBERT runs on it when `bert_model_path` names a
             # local HF model directory (mdm_amd/text_encoder.py; model/mdm.py:119 `self.clip_model = load_bert(bert_model_path)`)
+            # CLIP's text tower runs on it too when `clip_model_path` names a local CLIP file or HF directory (mdm_amd/clip_text.py)
             bert_model_path = kargs.get('bert_model_path', None)
-            if self.text_encoder_type == 'clip':
+            clip_model_path = kargs.get('clip_model_path', None)
+            if self.text_encoder_type == 'clip' and clip_model_path is not None:
+                self.clip_model = load_clip_text(clip_model_path, _native_lib=self._native_lib)
+            elif self.text_encoder_type == 'clip':
                 self.clip_model = self._try_load_clip(clip_version)
             elif bert_model_path is not None:
                 self.clip_model = load_bert(bert_model_path, _native_lib=self._native_lib)
@@ -313,6 +318,9 @@ class MDM(nn.Module):
         if getattr(self, 'clip_model', None) is None:
             raise RuntimeError("CLIP is not available in this environment: pass the cached embedding as "
                                "y['text_embed'] ([1, B, clip_dim]); see sample/generate.py:130-132")
+        if isinstance(self.clip_model, ClipText):             # the HIP encoder: no padding to 77, the rows behind an EOT move no bit
+            texts = self.clip_model.tokenize(raw_text, context_length=22 if self.dataset in ['humanml', 'kit'] else 77, truncate=True)
+            return self.clip_model.encode_text(texts).unsqueeze(0)
         import clip
         device = next(self.parameters()).device
         if self.dataset in ['humanml', 'kit']:
