@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import _native as nat
-from .evaluator import _ParamContainer
+from ._native_model import NativeModelMixin, _ParamContainer
 
 HEAD_DIM = 64
 MAX_TOKENS = 128           # include/mdm_hip.h mdm_clip_text_encode
@@ -115,7 +115,7 @@ class HfClipBpe:
 
 
 # ---- the encoder --------------------------------------------------------------------------------------------------------------------
-class ClipText(_ParamContainer):
+class ClipText(NativeModelMixin, _ParamContainer):
     """Parameters under OpenAI CLIP's text-side state-dict keys; `encode_text(tokens)` runs the HIP path and there is no eager forward."""
 
     def __init__(self, vocab, positions, width, layers, mlp, embed, tokenizer=None, _native_lib=None):
@@ -129,7 +129,6 @@ class ClipText(_ParamContainer):
                         embed=int(embed))
         self.tokenizer = tokenizer
         self._native_lib = _native_lib
-        self._prepared = None
         self._ws = {}
 
     @classmethod
@@ -166,53 +165,38 @@ class ClipText(_ParamContainer):
                            "forward and no image tower")
 
     # ---- native model ----------------------------------------------------------------------------------------------------------
-    def _lib(self):
-        return self._native_lib if self._native_lib is not None else nat.load_native()
+    def _native_version(self):
+        return self.version()
 
-    def _model(self):
+    def _build_native(self, keep):
         """The prepared tables (1/8 folded into the q rows -- a power of two: no bit changes --, the projection laid out
-        [embed, width]) and the C structs over them; rebuilt when a parameter was replaced, written or moved since."""
-        ver = self.version()
-        if self._prepared is None or self._prepared[0] != ver:
-            sd = {k: v.detach().float() for k, v in self.state_dict().items()}
-            keep, c = [], self.cfg
+        [embed, width]) and the C structs over them."""
+        sd = {k: v.detach().float() for k, v in self.state_dict().items()}
+        c = self.cfg
 
-            def own(t):          # own storage: 16-byte aligned, unaffected by later loads
-                t = t.contiguous().clone()
-                keep.append(t)
-                return t.data_ptr()
+        def own(t):          # own storage: 16-byte aligned, unaffected by later loads
+            t = t.contiguous().clone()
+            keep.append(t)
+            return t.data_ptr()
 
-            W = c["width"]
-            layers = (nat.MdmClipTextLayer * c["layers"])()
-            for n in range(c["layers"]):
-                p = f"transformer.resblocks.{n}."
-                qkv_w, qkv_b = sd[p + "attn.in_proj_weight"].clone(), sd[p + "attn.in_proj_bias"].clone()
-                qkv_w[:W] *= 0.125
-                qkv_b[:W] *= 0.125
-                layers[n] = nat.MdmClipTextLayer(
-                    ln1_g=own(sd[p + "ln_1.weight"]), ln1_b=own(sd[p + "ln_1.bias"]), qkv_w=own(qkv_w), qkv_b=own(qkv_b),
-                    out_w=own(sd[p + "attn.out_proj.weight"]), out_b=own(sd[p + "attn.out_proj.bias"]),
-                    ln2_g=own(sd[p + "ln_2.weight"]), ln2_b=own(sd[p + "ln_2.bias"]),
-                    fc_w=own(sd[p + "mlp.c_fc.weight"]), fc_b=own(sd[p + "mlp.c_fc.bias"]),
-                    proj_w=own(sd[p + "mlp.c_proj.weight"]), proj_b=own(sd[p + "mlp.c_proj.bias"]))
-            model = nat.MdmClipTextModel(
-                tok_emb=own(sd["token_embedding.weight"]), pos_emb=own(sd["positional_embedding"]), lnf_g=own(sd["ln_final.weight"]),
-                lnf_b=own(sd["ln_final.bias"]), text_proj=own(sd["text_projection"].t()), layers=layers, n_layers=c["layers"], dim=W,
-                n_heads=c["heads"], mlp=c["mlp"], vocab=c["vocab"], max_pos=c["positions"], embed=c["embed"])
-            self._prepared = (ver, model, (keep, layers))
-            self._ws = {}
-        return self._prepared[1]
-
-    def _workspace(self, lib, model, B, L, dev, stream):
-        key = (B, L, str(dev), stream)       # (per stream: two streams may be inside the encoder at once)
-        if key not in self._ws:
-            nbytes = lib.mdm_clip_text_workspace_bytes(nat.C.byref(model), B, L)
-            if nbytes == 0:
-                lib.check(-1, "mdm_clip_text_workspace_bytes")
-            if len(self._ws) >= 8:           # (prompt batches come in few shapes; an odd caller must not pile workspaces up)
-                self._ws = {}
-            self._ws[key] = (torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes)
-        return self._ws[key]
+        W = c["width"]
+        layers = (nat.MdmClipTextLayer * c["layers"])()
+        for n in range(c["layers"]):
+            p = f"transformer.resblocks.{n}."
+            qkv_w, qkv_b = sd[p + "attn.in_proj_weight"].clone(), sd[p + "attn.in_proj_bias"].clone()
+            qkv_w[:W] *= 0.125
+            qkv_b[:W] *= 0.125
+            layers[n] = nat.MdmClipTextLayer(
+                ln1_g=own(sd[p + "ln_1.weight"]), ln1_b=own(sd[p + "ln_1.bias"]), qkv_w=own(qkv_w), qkv_b=own(qkv_b),
+                out_w=own(sd[p + "attn.out_proj.weight"]), out_b=own(sd[p + "attn.out_proj.bias"]),
+                ln2_g=own(sd[p + "ln_2.weight"]), ln2_b=own(sd[p + "ln_2.bias"]),
+                fc_w=own(sd[p + "mlp.c_fc.weight"]), fc_b=own(sd[p + "mlp.c_fc.bias"]),
+                proj_w=own(sd[p + "mlp.c_proj.weight"]), proj_b=own(sd[p + "mlp.c_proj.bias"]))
+        keep.append(layers)
+        return nat.MdmClipTextModel(
+            tok_emb=own(sd["token_embedding.weight"]), pos_emb=own(sd["positional_embedding"]), lnf_g=own(sd["ln_final.weight"]),
+            lnf_b=own(sd["ln_final.bias"]), text_proj=own(sd["text_projection"].t()), layers=layers, n_layers=c["layers"], dim=W,
+            n_heads=c["heads"], mlp=c["mlp"], vocab=c["vocab"], max_pos=c["positions"], embed=c["embed"])
 
     # ---- the encoder -----------------------------------------------------------------------------------------------------------
     def check_tokens(self, tokens):
@@ -242,16 +226,13 @@ class ClipText(_ParamContainer):
         B, L = ids.shape
         lib, model = self._lib(), self._model()
         dev = self.device
-        emulation = not lib.path.endswith(nat.LIB_NAME)
-        if not emulation and dev.type != "cuda":
-            raise nat.MdmError("the MI355X HIP path needs the CLIP text encoder's parameters on a cuda (ROCm) device; got " + str(dev))
-        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+        stream = self._stream(lib, dev, "the CLIP text encoder's parameters")
         ids_dev, lens_dev = ids.to(dev), lens.to(dev)
         out = torch.empty((B, self.cfg["embed"]), dtype=torch.float32, device=dev)
         step = max(1, MAX_ROWS // L)
         for b0 in range(0, B, step):
             n = min(step, B - b0)
-            ws, nbytes = self._workspace(lib, model, n, L, dev, stream)
+            ws, nbytes = self._workspace("mdm_clip_text_workspace_bytes", model, n, L, dev=dev, stream=stream, cache=True)
             lib.check(lib.mdm_clip_text_encode(nat.C.byref(model), ids_dev[b0:b0 + n].data_ptr(), lens_dev[b0:b0 + n].data_ptr(),
                                                out[b0:b0 + n].data_ptr(), n, L, ws.data_ptr(), nbytes, stream), "mdm_clip_text_encode")
         return out

@@ -43,6 +43,23 @@ template <class K> inline int rt_allow_lds(K kernel, size_t bytes) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The workspace convention of every entry point outside the MDM model (smpl, evaluator, text, clip text, stgcn, gru recogniser): a
+// caller-owned block of ws_bytes_of(floats) bytes at any address; the floats start at its first 16-byte boundary.
+inline size_t ws_bytes_of(size_t floats) { return floats * sizeof(float) + 64; }
+inline float* ws_floats(void* ws) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15); }
+
+// The weight tables of such a model's struct: each of ptrs[0 .. n) non-null and 16-byte aligned, or a failure that names the field.
+// `f` is the entry point's "<function>: " prefix, `group` what stands in front of the field's name ("layers[3]." or nothing).
+inline int check_weight_ptrs(const std::string& f, const void* const* ptrs, const char* const* names, int n,
+                             const std::string& group = std::string()) {
+  for (int i = 0; i < n; ++i) {
+    if (ptrs[i] == nullptr) return fail(MDM_EINVAL, f + "null weight pointer " + group + names[i]);
+    if ((reinterpret_cast<uintptr_t>(ptrs[i]) & 15) != 0)
+      return fail(MDM_EINVAL, f + "weight pointer " + group + names[i] + " must be 16-byte aligned");
+  }
+  return 0;
+}
+
 // launcher return codes -1 / -3 of the dynamic-LDS opt-in (common.h rt_dyn_lds_once)
 inline int lds_fail(int rc, const char* what) {
   if (rc == -3)

@@ -748,6 +748,14 @@ inline void launch_gemm_f32_t(const AL& al, const BL& bl, const EP& ep, int M, i
   MDM_LAUNCH(kfn, dim3(tiles_m * tiles_n), dim3(GEMM_THREADS), gemm_f32_lds_total(128, X3), stream, al, bl, ep, M, N, K, tiles_n, weight_is_a);
   }
 }
+// The exact-fp32 kernel on its 64-row tile whatever the output's size, for callers that must not let launch_gemm_f32_t's size rule
+// choose the tile shape (each says why where it calls this).
+template <class AL, class BL, class EP>
+inline void launch_gemm_f32_rows64(const AL& al, const BL& bl, const EP& ep, int M, int N, int K, hipStream_t stream) {
+  const int tm = (M + 63) / 64, tn = (N + 63) / 64;
+  auto kfn = &gemm_f32_kernel<AL, BL, EP, 64, false, 1>;
+  MDM_LAUNCH(kfn, dim3(tm * tn), dim3(GEMM_THREADS), gemm_f32_lds_total(64, false), stream, al, bl, ep, M, N, K, tn, 0);
+}
 template <class AL, class BL, class EP>
 inline void launch_gemm_f32(const AL& al, const BL& bl, const EP& ep, int M, int N, int K, hipStream_t stream,
                             bool x3 = false, bool weight_is_a = false) {

@@ -7,7 +7,7 @@ namespace {
 
 struct GruClsPlan {
   size_t gi, seq, hl;      // floats of the three workspace buffers
-  size_t bytes() const { return (gi + seq + hl) * sizeof(float) + 64; }
+  size_t bytes() const { return ws_bytes_of(gi + seq + hl); }
 };
 
 // Validation shared by mdm_gru_cls_workspace_bytes and mdm_gru_cls_forward; 0 or a negative code with the message set
@@ -23,22 +23,15 @@ int gru_cls_plan(const char* fn, const mdm_gru_cls_model_t* m, int B, int T, Gru
   if (m->input_size < 1) return fail(MDM_EINVAL, f + "input_size must be at least 1");
   if (m->mid < 1 || m->mid > GRU_TAIL_MAX) return fail(MDM_EUNSUPPORTED, f + "mid must be between 1 and 64");
   if (m->num_class < 1 || m->num_class > GRU_TAIL_MAX) return fail(MDM_EUNSUPPORTED, f + "num_class must be between 1 and 64");
-  auto check = [&](const void* q, const std::string& name) {
-    if (q == nullptr) return fail(MDM_EINVAL, f + "null weight pointer " + name);
-    if ((reinterpret_cast<uintptr_t>(q) & 15) != 0) return fail(MDM_EINVAL, f + "weight pointer " + name + " must be 16-byte aligned");
-    return 0;
-  };
   static const char* names[] = {"w_ih", "w_hh", "b_ih", "b_hh"};
   for (int l = 0; l < m->num_layers; ++l) {
     const mdm_gru_cls_layer_t& y = m->layers[l];
     const void* ptrs[] = {y.w_ih, y.w_hh, y.b_ih, y.b_hh};
-    for (int i = 0; i < 4; ++i)
-      if (int rc = check(ptrs[i], "layers[" + std::to_string(l) + "]." + names[i])) return rc;
+    if (int rc = check_weight_ptrs(f, ptrs, names, 4, "layers[" + std::to_string(l) + "].")) return rc;
   }
   const void* top[] = {m->lin1_w, m->lin1_b, m->lin2_w, m->lin2_b};
   static const char* top_names[] = {"lin1_w", "lin1_b", "lin2_w", "lin2_b"};
-  for (int i = 0; i < 4; ++i)
-    if (int rc = check(top[i], top_names[i])) return rc;
+  if (int rc = check_weight_ptrs(f, top, top_names, 4)) return rc;
   // (row counts and offsets inside the GEMM are 32-bit)
   const int64_t rows = (int64_t)B * T;
   if (rows * 3 * m->hidden_size >= (1ll << 31) || rows * m->input_size >= (1ll << 31))
@@ -53,9 +46,7 @@ int gru_cls_plan(const char* fn, const mdm_gru_cls_model_t* m, int B, int T, Gru
 template <class AL, class BL>
 int gru_cls_gemm(const AL& al, const BL& bl, const float* bias, float* out, int M, int N, int K, hipStream_t s) {
   LeakyEpilogue ep{out, bias, N, 0};
-  const int tm = (M + 63) / 64, tn = (N + 63) / 64;
-  auto kfn = &gemm_f32_kernel<AL, BL, LeakyEpilogue, 64, false, 1>;
-  MDM_LAUNCH(kfn, dim3(tm * tn), dim3(GEMM_THREADS), gemm_f32_lds_total(64, false), s, al, bl, ep, M, N, K, tn, 0);
+  launch_gemm_f32_rows64(al, bl, ep, M, N, K, s);
   return rt_launch_status();
 }
 
@@ -92,7 +83,7 @@ int mdm_gru_cls_forward(const mdm_gru_cls_model_t* m, const float* x, const int3
   hipStream_t s = static_cast<hipStream_t>(stream);
   ChainGuard chain_guard(stream);
   const int H = m->hidden_size, I = m->input_size, L = m->num_layers;
-  float* gi = eval_ws(ws);          // [B T][3H]  the layer's input projections
+  float* gi = ws_floats(ws);          // [B T][3H]  the layer's input projections
   float* seq = gi + p.gi;           // [B][T][H]  the layer's outputs: read by the next layer's projection, then overwritten by its recurrence
   float* hl = seq + p.seq;          // [B][H]     the last layer's output at frame len_b - 1
   const int M = B * T;

@@ -550,63 +550,6 @@ int mdm_randn(float* out, const float* init, const float* eps, float a, float s,
 }
 #include "loops.h"
 
-#ifdef MDM_PROBES
-int mdm_debug_set(int what, int value) {
-  // 0 (GEMM ablations), 2 (4-wave workgroups), 6 (sync / pipe probe), 8 (start delay) of gemm_x3.h and 3 (ablations of
-  // attention_x3.h): experiments that were removed with their code (lab/README.md) -- refused, so that an old A/B script does not
-  // measure the product against itself
-  if (what == 0 || what == 2 || what == 3 || what == 6 || what == 8)
-    return fail(MDM_EINVAL, "mdm_debug_set: code " + std::to_string(what) + " belonged to a " +
-                                (what == 3 ? "attention_x3.h" : "gemm_x3.h") + " experiment that has been removed");
-  if (what == 1) g_x3_reuse_planes = value;
-  if (what == 4) g_f6_reference = value;
-  if (what == 5) g_f6_linear = value;
-#ifndef MDM_EMU
-  if (what == 9) { x3s_tl_target() = value; x3s_tl_count() = 0; }   // gemm_x3s.h timeline probe: stamp the value-th launch from now
-  if (what == 10) { xb_tl_target() = value; xb_tl_count() = 0; }    // xattn_block.h timeline probe
-  if (what == 11) { sb_tl_target() = value; sb_tl_count() = 0; }    // selfattn_block.h timeline probe (self and cross launches)
-#endif
-  return MDM_OK;
-}
-
-int mdm_debug_get(int idx, double* out) {   // timeline stamps of the x3s / xattn / selfattn probes
-#ifndef MDM_EMU
-  if (idx >= 300000) {   // selfattn_block.h timeline stamps (read once at idx == 300000, then served from the host copy)
-    static std::vector<unsigned long long> tl(8 * SB_TL_WGS);
-    if (idx - 300000 >= 8 * SB_TL_WGS || out == nullptr) return fail(MDM_EINVAL, "mdm_debug_get: bad timeline index");
-    if (idx == 300000 && (hipDeviceSynchronize() != hipSuccess ||
-                          hipMemcpyFromSymbol(tl.data(), HIP_SYMBOL(g_sb_tl), tl.size() * sizeof(unsigned long long)) != hipSuccess))
-      return fail(MDM_EHIP, "mdm_debug_get: reading the timeline failed");
-    *out = (double)tl[idx - 300000];
-    return MDM_OK;
-  }
-  if (idx >= 200000) {   // xattn_block.h timeline stamps (read once at idx == 200000, then served from the host copy)
-    static std::vector<unsigned long long> tl(8 * XB_TL_WGS);
-    if (idx - 200000 >= 8 * XB_TL_WGS || out == nullptr) return fail(MDM_EINVAL, "mdm_debug_get: bad timeline index");
-    if (idx == 200000 && (hipDeviceSynchronize() != hipSuccess ||
-                          hipMemcpyFromSymbol(tl.data(), HIP_SYMBOL(g_xb_tl), tl.size() * sizeof(unsigned long long)) != hipSuccess))
-      return fail(MDM_EHIP, "mdm_debug_get: reading the timeline failed");
-    *out = (double)tl[idx - 200000];
-    return MDM_OK;
-  }
-  if (idx >= 100) {   // gemm_x3s.h timeline stamps (read once at idx == 100, then served from the host copy)
-    static std::vector<unsigned long long> tl(4 * X3S_TL_WGS);
-    if (idx - 100 >= 4 * X3S_TL_WGS || out == nullptr) return fail(MDM_EINVAL, "mdm_debug_get: bad timeline index");
-    if (idx == 100 && (hipDeviceSynchronize() != hipSuccess ||
-                       hipMemcpyFromSymbol(tl.data(), HIP_SYMBOL(g_x3s_tl), tl.size() * sizeof(unsigned long long)) != hipSuccess))
-      return fail(MDM_EHIP, "mdm_debug_get: reading the timeline failed");
-    *out = (double)tl[idx - 100];
-    return MDM_OK;
-  }
-  return fail(MDM_EINVAL, "mdm_debug_get: not a timeline index");
-#else
-  if (out != nullptr) *out = 0.0;
-  (void)idx;
-  return MDM_OK;
-#endif
-}
-#endif
-
 int mdm_profile_enable(mdm_model_t* m, int on) {
   if (m == nullptr) return fail(MDM_EINVAL, "mdm_profile_enable: null model");
   m->prof.on = on != 0;
@@ -681,57 +624,6 @@ int mdm_linear_x3(const float* in, const float* w, const float* bias, const floa
                           1.f, 0, s);
 }
 
-#ifdef MDM_PROBES
-size_t mdm_linear_f16f6_scratch_bytes(int32_t M, int32_t N, int32_t K) {
-  if (M <= 0 || N <= 0 || K <= 0 || K % 32 != 0) return 0;
-  // A planes | W as fragment-ordered planes (fast kernel) | W as row-major planes (reference kernel)
-  return f6_plane_bytes(M, K) + 2 * align_up(x3_packed_weight_elems(N, K) * 2, 256) + f6_plane_bytes(N, K);
-}
-
-int mdm_linear_f16f6(const float* in, const float* w, const float* bias, const float* res, float* out, int32_t M,
-                     int32_t N, int32_t K, int32_t act, void* scratch, size_t scratch_bytes, void* stream) {
-  ChainGuard chain_guard(stream);
-  if (!in || !w || !bias || !out || !scratch || M <= 0 || N <= 0 || K <= 0) return fail(MDM_EINVAL, "mdm_linear_f16f6: bad argument");
-  if (K % 32 != 0) return fail(MDM_EINVAL, "mdm_linear_f16f6: K must be a multiple of 32");
-  if (act != ACT_NONE && act != ACT_GELU && act != ACT_SILU) return fail(MDM_EINVAL, "mdm_linear_f16f6: bad activation");
-  if (scratch_bytes < mdm_linear_f16f6_scratch_bytes(M, N, K)) return fail(MDM_ENOSPC, "mdm_linear_f16f6: scratch too small");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(scratch);
-  const F6Planes pa = f6_carve(base, M, K);
-  p16_t* wfh = reinterpret_cast<p16_t*>(base + f6_plane_bytes(M, K));
-  p16_t* wfl = reinterpret_cast<p16_t*>(base + f6_plane_bytes(M, K) + align_up(x3_packed_weight_elems(N, K) * 2, 256));
-  const F6Planes pw = f6_carve(base + f6_plane_bytes(M, K) + 2 * align_up(x3_packed_weight_elems(N, K) * 2, 256), N, K);
-  // the production skeleton (gemm_x3_kernel<..., X3_OUT_F32 | X3_F6>) where its epilogues exist; else the one-wave-per-tile reference
-  const bool fast = !g_f6_reference && N % 4 == 0 && ((act == ACT_NONE) || (act == ACT_GELU && res == nullptr));
-  if (!g_x3_reuse_planes) {
-    MDM_LAUNCH(pack_f16f6_kernel, dim3((M * (K / 32) + 255) / 256), dim3(256), 0, s, in, pa, M, K, K);
-    if (int rc = rt_launch_status()) return rc;
-    if (fast) {
-      const int npad = (N + 31) / 32 * 32;
-      MDM_LAUNCH(pack_weight_f16f6_kernel, dim3((npad * (K / 32) + 255) / 256), dim3(256), 0, s, w, wfh, wfl, N, K);
-    } else {
-      MDM_LAUNCH(pack_f16f6_kernel, dim3((N * (K / 32) + 255) / 256), dim3(256), 0, s, w, pw, N, K, K);
-    }
-    if (int rc = rt_launch_status()) return rc;
-  }
-  if (fast) {
-    X3Call c; c.out = out; c.bias = bias; c.res_f32 = res; c.N = N;
-    X3Epilogue ep = x3_epilogue(c);
-    ep.acc_scale = 1.f;   // (pack_weight_f16f6_kernel's planes are unscaled: no 2^8 to undo)
-    const X3Operand a{reinterpret_cast<const p16_t*>(pa.h16), reinterpret_cast<const p16_t*>(pa.rec)};
-    const int rc = launch_gemm_f16f6(a, X3Weights{wfh, wfl}, ep, M, N, K, act, s);
-    if (rc == -1 || rc == -3) return lds_fail(rc, "mdm_linear_f16f6");
-    if (rc == -2) return fail(MDM_EUNSUPPORTED, "mdm_linear_f16f6: unsupported (activation, residual) combination");
-    return rt_launch_status();
-  }
-  const dim3 grid((N + 31) / 32, (M + 31) / 32);
-  if (act == ACT_GELU) MDM_LAUNCH(gemm_f16f6_ref_kernel<ACT_GELU>, grid, dim3(64), 0, s, pa, pw, bias, res, out, M, N, K);
-  else if (act == ACT_SILU) MDM_LAUNCH(gemm_f16f6_ref_kernel<ACT_SILU>, grid, dim3(64), 0, s, pa, pw, bias, res, out, M, N, K);
-  else MDM_LAUNCH(gemm_f16f6_ref_kernel<ACT_NONE>, grid, dim3(64), 0, s, pa, pw, bias, res, out, M, N, K);
-  return rt_launch_status();
-}
-#endif
-
 int mdm_layernorm(float* x, const float* gamma, const float* beta, int32_t rows, int32_t D, void* stream) {
   ChainGuard chain_guard(stream);
   if (!x || !gamma || !beta || rows <= 0 || D % 256 != 0) return fail(MDM_EINVAL, "mdm_layernorm: bad argument");
@@ -770,766 +662,15 @@ int mdm_attention_x3(const float* qkv, float* out, const int32_t* lengths, int32
   return launch_attention_x3(nullptr, qp, lengths, nseq, B, S, D, out, nullptr, nullptr, s);
 }
 
+}  // extern "C"
+
+// The entry points that are not MDM's own, one file per model (each with its helpers in an anonymous namespace): the probe
+// library's, then SMPL, the HumanML3D evaluator, the two text encoders, ST-GCN and the GRU recogniser.
 #ifdef MDM_PROBES
-// mdm_attention_x3 with the kernel form, the lead tokens and the outputs chosen by the caller: fp32 rows and / or hi, lo planes.
-// tests/test_*_attention_wide.py hold the wide form against the 4-wave kernel bit for bit.
-int mdm_probe_attention_x3(const float* qkv, float* out, void* out_hi, void* out_lo, const int32_t* lengths, int32_t nseq, int32_t B,
-                           int32_t S, int32_t D, int32_t H, int32_t lead, int32_t wide, void* scratch, size_t scratch_bytes,
-                           void* stream) {
-  ChainGuard chain_guard(stream);
-  if (!qkv || (!out && !out_hi) || (out_hi == nullptr) != (out_lo == nullptr) || !scratch || nseq <= 0 || B <= 0 || S <= 0 || H <= 0 ||
-      lead < 0)
-    return fail(MDM_EINVAL, "mdm_probe_attention_x3: bad argument");
-  if (D != H * AX_HD) return fail(MDM_EUNSUPPORTED, "attention: head_dim must be 128");
-  if (scratch_bytes < mdm_attention_x3_scratch_bytes(nseq, S, D)) return fail(MDM_ENOSPC, "mdm_probe_attention_x3: scratch too small");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int NKT = (S + 31) / 32, SP = 32 * NKT;
-  const size_t plane = (size_t)nseq * SP * D;
-  p16_t* q = static_cast<p16_t*>(scratch);
-  QkvPlanes qp{q, q + plane, q + 2 * plane, q + 3 * plane, q + 4 * plane, q + 5 * plane, SP, NKT, H};
-  MDM_LAUNCH(qkv_pack_kernel, dim3((int)std::min<size_t>((plane + 255) / 256, 4096)), dim3(256), 0, s, qkv, qp, nseq, S, D);
-  if (int rc = rt_launch_status()) return rc;
-  return launch_attention_x3(nullptr, qp, lengths, nseq, B, S, D, out, static_cast<p16_t*>(out_hi), static_cast<p16_t*>(out_lo), s, lead,
-                             /*direct=*/false, wide != 0);
-}
-
-// in_proj alone (the non-folded instantiation of layer 0): fp32 tokens [nseq * S][D] and in_proj weights [3D][D] -> the
-// attention operand planes, written to `planes_dev` (6 planes of nseq * SP * D 16-bit elements: qh ql kh kl vh vl).
-// `scratch_dev`: 4 * nseq * S * D + 12 * D * D bytes.  tools/in_proj_determinism.py compares repeated runs bit for bit.
-int mdm_probe_in_proj(const float* tokens, const float* w, const float* bias, void* planes_dev, int32_t nseq, int32_t S,
-                      int32_t D, void* scratch_dev, void* stream) {
-  ChainGuard chain_guard(stream);
-  if (!tokens || !w || !bias || !planes_dev || !scratch_dev || nseq <= 0 || S <= 0 || D % 256 != 0) return fail(MDM_EINVAL, "mdm_probe_in_proj");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t n = (size_t)nseq * S * D;
-  p16_t* ah = static_cast<p16_t*>(scratch_dev);
-  p16_t* al = ah + n;
-  p16_t* wh = al + n;
-  p16_t* wl = wh + (size_t)3 * D * D;
-  if (!g_x3_reuse_planes) {
-    if (int rc = launch_split(tokens, ah, al, n, s)) return rc;
-    if (int rc = launch_pack_weights(w, wh, wl, 3 * D, D, s)) return rc;
-  }
-  const int H = D / AX_HD, NKT = (S + 31) / 32, SP = 32 * NKT;
-  const size_t plane = (size_t)nseq * SP * D;
-  p16_t* q = static_cast<p16_t*>(planes_dev);
-  QkvPlanes qp{q, q + plane, q + 2 * plane, q + 3 * plane, q + 4 * plane, q + 5 * plane, SP, NKT, H};
-  return launch_in_proj_x3(nullptr, X3Operand{ah, al}, X3Weights{wh, wl}, bias, qp, nseq, S, D, 0.08838834764831845f, s);
-}
+#include "probe_api.h"
 #endif
-
-int mdm_recover_from_ric(const float* x, const float* mean, const float* stdv, float* out, int32_t B, int32_t T,
-                         int32_t njoints_feat, int32_t joints, void* stream) {
-  ChainGuard chain_guard(stream);
-  if (!x || !mean || !stdv || !out || B <= 0 || T <= 0 || joints < 1) return fail(MDM_EINVAL, "mdm_recover_from_ric: bad argument");
-  if (njoints_feat < 4 + 3 * (joints - 1)) return fail(MDM_EINVAL, "mdm_recover_from_ric: feature width too small for the joint count");
-  if (T > 1024) return fail(MDM_EUNSUPPORTED, "mdm_recover_from_ric: at most 1024 frames");
-  auto k = &recover_from_ric_kernel;
-  MDM_LAUNCH(k, dim3(B), dim3(256), (size_t)3 * T * sizeof(float), static_cast<hipStream_t>(stream), x, mean, stdv, out, T,
-             njoints_feat, joints);
-  return rt_launch_status();
-}
-
-int mdm_rot6d_to_smpl_joints(const float* x, const uint8_t* mask, const float* rest_joints, const int32_t* parents, float* out,
-                             int32_t B, int32_t T, int32_t njoints_in, int32_t J, void* stream) {
-  if (!x || !rest_joints || !parents || !out) return fail(MDM_EINVAL, "mdm_rot6d_to_smpl_joints: null pointer");
-  if (B <= 0 || T <= 0 || J < 1) return fail(MDM_EINVAL, "mdm_rot6d_to_smpl_joints: need B >= 1, T >= 1 and J >= 1");
-  if (njoints_in != J + 1)
-    return fail(MDM_EINVAL, "mdm_rot6d_to_smpl_joints: njoints_in must be J + 1 (the joint rotations, then the translation row)");
-  if (J > kSmplMaxJoints) return fail(MDM_EUNSUPPORTED, "mdm_rot6d_to_smpl_joints: at most 24 joints");
-  if (T > 4096 || (int64_t)B * T > (1 << 24)) return fail(MDM_EUNSUPPORTED, "mdm_rot6d_to_smpl_joints: at most 4096 frames and 2^24 frames in all");
-  if (parents[0] != -1) return fail(MDM_EINVAL, "mdm_rot6d_to_smpl_joints: parents[0] must be -1 (the root)");
-  for (int i = 1; i < J; ++i)
-    if (parents[i] < 0 || parents[i] >= i)
-      return fail(MDM_EINVAL, "mdm_rot6d_to_smpl_joints: parents[" + std::to_string(i) + "] must lie in [0, " + std::to_string(i) + ")");
-  SmplFkTables tab;
-  if (smpl_fk_tables(rest_joints, parents, J, tab) < 0) return fail(MDM_EUNSUPPORTED, "mdm_rot6d_to_smpl_joints: tree needs too many live transforms");
-  ChainGuard chain_guard(stream);
-  auto k = &smpl_joints_kernel;
-  MDM_LAUNCH(k, dim3((unsigned)(((int64_t)B * T + kSmplLanes - 1) / kSmplLanes)), dim3(kSmplLanes), 0, static_cast<hipStream_t>(stream),
-             x, mask, out, B, T, J, tab);
-  return rt_launch_status();
-}
-
-}  // extern "C"
-
-namespace {
-
-struct SmplPlan {
-  int J, V, Vpad, KP, NA;          // NA: rows of the extended joint list
-  bool joints, need_sel, need_mesh;
-  size_t feat, aws, delta, allj, mesh;   // workspace extents, floats
-};
-
-// Validation shared by mdm_smpl_workspace_bytes and mdm_smpl_forward; 0 or a negative code with the message set.
-int smpl_plan(const char* fn, const mdm_smpl_model_t* m, const mdm_smpl_call_t* c, int B, int T, SmplPlan& p) {
-  const std::string f = std::string(fn) + ": ";
-  if (m == nullptr || c == nullptr) return fail(MDM_EINVAL, f + "null model or call");
-  if (B <= 0 || T <= 0) return fail(MDM_EINVAL, f + "need B >= 1 and T >= 1");
-  if (T > 4096 || (int64_t)B * T > (1 << 24)) return fail(MDM_EUNSUPPORTED, f + "at most 4096 frames and 2^24 frames in all");
-  if (m->J < 1) return fail(MDM_EINVAL, f + "need J >= 1");
-  if (m->J > kSmplMaxJoints) return fail(MDM_EUNSUPPORTED, f + "at most 24 joints");
-  if (m->V < 1 || m->V > (1 << 20)) return fail(MDM_EINVAL, f + "the vertex count V must lie in [1, 2^20]");
-  if (m->n_sel < 0 || m->n_sel > 32) return fail(MDM_EINVAL, f + "n_sel must lie in [0, 32]");
-  if (m->n_extra < 0 || m->n_extra > kSmplMaxExtra) return fail(MDM_EINVAL, f + "n_extra must lie in [0, 16]");
-  if (m->parents == nullptr) return fail(MDM_EINVAL, f + "null parents");
-  if (m->parents[0] != -1) return fail(MDM_EINVAL, f + "parents[0] must be -1 (the root)");
-  for (int i = 1; i < m->J; ++i)
-    if (m->parents[i] < 0 || m->parents[i] >= i)
-      return fail(MDM_EINVAL, f + "parents[" + std::to_string(i) + "] must lie in [0, " + std::to_string(i) + ")");
-  if (c->pose_rep < MDM_SMPL_ROT6D || c->pose_rep > MDM_SMPL_ROTQUAT) return fail(MDM_EINVAL, f + "pose_rep must be one of MDM_SMPL_ROT6D .. MDM_SMPL_ROTQUAT");
-  if (!c->glob && c->glob_rot_mat == nullptr) return fail(MDM_EINVAL, f + "glob = 0 needs glob_rot_mat");
-  if (c->n_points < 0 || c->n_points > kSmplMaxPoints) return fail(MDM_EINVAL, f + "n_points must lie in [0, 64]");
-  p.J = m->J;
-  p.V = m->V;
-  p.Vpad = (m->V + 31) & ~31;
-  p.KP = smpl_feat_kp(m->J);
-  p.NA = m->J + m->n_sel + m->n_extra;
-  p.joints = c->n_points > 0;
-  p.need_sel = p.need_mesh = false;
-  if (p.joints) {
-    if (c->point_map == nullptr) return fail(MDM_EINVAL, f + "n_points > 0 needs point_map");
-    if (c->root_point < 0 || c->root_point >= c->n_points) return fail(MDM_EINVAL, f + "root_point must lie in [0, n_points)");
-    for (int i = 0; i < c->n_points; ++i) {
-      const int s = c->point_map[i];
-      if (s < 0 || s >= p.NA)
-        return fail(MDM_EINVAL, f + "point_map[" + std::to_string(i) + "] = " + std::to_string(s) + " is outside the joint list of " +
-                                    std::to_string(p.NA) + " (J + n_sel + n_extra)");
-      if (s >= m->J + m->n_sel) p.need_mesh = true;
-      else if (s >= m->J) p.need_sel = true;
-    }
-  }
-  p.feat = (size_t)B * p.KP * T;
-  p.aws = (size_t)B * 12 * kSmplMaxJoints * T;
-  p.delta = (size_t)B * 3 * T;
-  p.allj = (size_t)B * p.NA * 3 * T;
-  p.mesh = p.need_mesh ? (size_t)kSkinChunkTiles * kSkinFrames * 3 * p.V : 0;
-  return 0;
-}
-
-size_t smpl_plan_bytes(const SmplPlan& p) { return (p.feat + p.aws + p.delta + p.allj + p.mesh) * sizeof(float) + 64; }
-
-template <int REP> void launch_smpl_pose(const SmplPoseArgs& a, hipStream_t s) {
-  auto k = &smpl_pose_kernel<REP>;
-  MDM_LAUNCH(k, dim3((unsigned)(((int64_t)a.B * a.T + kSmplLanes - 1) / kSmplLanes)), dim3(kSmplLanes), 0, s, a);
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t mdm_smpl_workspace_bytes(const mdm_smpl_model_t* model, const mdm_smpl_call_t* call, int32_t B, int32_t T) {
-  SmplPlan p;
-  if (smpl_plan("mdm_smpl_workspace_bytes", model, call, B, T, p) != 0) return 0;
-  return smpl_plan_bytes(p);
-}
-
-int mdm_smpl_forward(const mdm_smpl_model_t* m, const mdm_smpl_call_t* c, const float* x, const uint8_t* mask, const float* betas,
-                     float* out, float* rot_out, int32_t B, int32_t T, int32_t rows_x, int32_t feats_x, void* ws, size_t ws_bytes,
-                     void* stream) {
-  const char* fn = "mdm_smpl_forward";
-  SmplPlan p;
-  if (int rc = smpl_plan(fn, m, c, B, T, p)) return rc;
-  if (!x || !out || !ws) return fail(MDM_EINVAL, "mdm_smpl_forward: null x, out or workspace");
-  if (!m->j0 || !m->jdirs) return fail(MDM_EINVAL, "mdm_smpl_forward: null j0 or jdirs table");
-  const bool skin = !p.joints || p.need_mesh;
-  if (skin && (!m->blend || !m->weights_t)) return fail(MDM_EINVAL, "mdm_smpl_forward: null blend or weights_t table");
-  if (p.need_sel && (!m->sel_blend || !m->sel_weights_t)) return fail(MDM_EINVAL, "mdm_smpl_forward: the map names a selected vertex: null sel_blend or sel_weights_t table");
-  if (p.need_mesh && !m->extra_t) return fail(MDM_EINVAL, "mdm_smpl_forward: the map names a regressed joint: null extra_t table");
-  const int NR = c->glob ? p.J : p.J - 1;
-  const int has_trans = c->translation ? 1 : 0;
-  if (rows_x != NR + has_trans)
-    return fail(MDM_EINVAL, "mdm_smpl_forward: x has " + std::to_string(rows_x) + " rows; need " + std::to_string(NR) +
-                                " rotation rows" + (has_trans ? " and the translation row" : ""));
-  if (feats_x != smpl_rep_feats(c->pose_rep))
-    return fail(MDM_EINVAL, "mdm_smpl_forward: x has " + std::to_string(feats_x) + " features per row; this pose_rep has " +
-                                std::to_string(smpl_rep_feats(c->pose_rep)));
-  if (NR < 1) return fail(MDM_EINVAL, "mdm_smpl_forward: no rotation row");
-  if (ws_bytes < smpl_plan_bytes(p)) return fail(MDM_ENOSPC, "mdm_smpl_forward: workspace too small (mdm_smpl_workspace_bytes)");
-  SmplFkTables tab;
-  {
-    float zero[kSmplMaxJoints * 3] = {};
-    if (smpl_fk_tables(zero, m->parents, p.J, tab) < 0) return fail(MDM_EUNSUPPORTED, "mdm_smpl_forward: tree needs too many live transforms");
-  }
-  float* w = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15);
-  float* feat = w;
-  float* aws = feat + p.feat;
-  float* delta = aws + p.aws;
-  float* allj = delta + p.delta;
-  float* mesh = allj + p.allj;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  ChainGuard chain_guard(stream);
-
-  SmplPoseArgs pa;
-  pa.x = x; pa.mask = mask; pa.betas = betas; pa.j0 = m->j0; pa.jdirs = m->jdirs;
-  pa.feat = feat; pa.aws = aws; pa.joints = allj; pa.delta = delta; pa.rot_out = rot_out;
-  pa.B = B; pa.T = T; pa.J = p.J; pa.NR = NR; pa.F = feats_x; pa.KP = p.KP; pa.joints_rows = p.NA;
-  pa.glob = c->glob ? 1 : 0; pa.has_trans = has_trans; pa.add_trans = has_trans && c->vertstrans ? 1 : 0;
-  pa.beta1 = c->beta1;
-  for (int i = 0; i < 9; ++i) pa.grot[i] = c->glob ? 0.f : c->glob_rot_mat[i];
-  for (int i = 0; i < kSmplMaxJoints; ++i) {
-    pa.parent[i] = i < p.J && i > 0 ? m->parents[i] : 0;
-    pa.pslot[i] = tab.pslot[i];
-    pa.oslot[i] = tab.oslot[i];
-  }
-  switch (c->pose_rep) {
-    case MDM_SMPL_ROT6D: launch_smpl_pose<kRepRot6d>(pa, s); break;
-    case MDM_SMPL_ROTVEC: launch_smpl_pose<kRepRotvec>(pa, s); break;
-    case MDM_SMPL_ROTMAT: launch_smpl_pose<kRepRotmat>(pa, s); break;
-    default: launch_smpl_pose<kRepRotquat>(pa, s); break;
-  }
-  if (int rc = rt_launch_status()) return rc;
-
-  const int tps = (T + kSkinFrames - 1) / kSkinFrames, ntiles = B * tps;
-  SmplSkinArgs sa;
-  sa.feat = feat; sa.aws = aws; sa.delta = delta; sa.mask = mask;
-  sa.T = T; sa.KP = p.KP; sa.tiles_per_sample = tps;
-  auto skin_k = &smpl_skin_kernel;
-  if (!p.joints) {                       // 'vertices': the mesh is the output
-    sa.blend = m->blend; sa.wt = m->weights_t; sa.out = out; sa.V = p.V; sa.Vpad = p.Vpad;
-    sa.tile0 = 0; sa.mode = 0; sa.out_rows = p.V; sa.row_off = 0; sa.finish = 1;
-    MDM_LAUNCH(skin_k, dim3(ntiles, (p.Vpad / 32 + kSkinTiles - 1) / kSkinTiles), dim3(kSkinWaves * 64), 0, s, sa);
-    return rt_launch_status();
-  }
-  if (p.need_sel) {                      // the selected vertices, skinned from their gathered tables into the joint list
-    sa.blend = m->sel_blend; sa.wt = m->sel_weights_t; sa.out = allj; sa.V = m->n_sel; sa.Vpad = (m->n_sel + 31) & ~31;
-    sa.tile0 = 0; sa.mode = 0; sa.out_rows = p.NA; sa.row_off = p.J; sa.finish = 0;
-    MDM_LAUNCH(skin_k, dim3(ntiles, 1), dim3(kSkinWaves * 64), 0, s, sa);
-    if (int rc = rt_launch_status()) return rc;
-  }
-  if (p.need_mesh) {                     // the regressed joints: the mesh of 16 frame tiles at a time, then a fixed-order reduction
-    sa.blend = m->blend; sa.wt = m->weights_t; sa.out = mesh; sa.V = p.V; sa.Vpad = p.Vpad;
-    sa.mode = 1; sa.out_rows = 0; sa.row_off = 0; sa.finish = 0;
-    auto extra_k = &smpl_extra_kernel;
-    for (int t0 = 0; t0 < ntiles; t0 += kSkinChunkTiles) {
-      const int n = std::min(kSkinChunkTiles, ntiles - t0);
-      sa.tile0 = t0;
-      MDM_LAUNCH(skin_k, dim3(n, (p.Vpad / 32 + kSkinTiles - 1) / kSkinTiles), dim3(kSkinWaves * 64), 0, s, sa);
-      MDM_LAUNCH(extra_k, dim3(n, 3, m->n_extra), dim3(256), 0, s, (const float*)mesh, m->extra_t, allj, (int)T, p.V, (int)m->n_extra, tps, t0, p.NA,
-                 p.J + m->n_sel);
-      if (int rc = rt_launch_status()) return rc;
-    }
-  }
-  SmplPointMap map;
-  for (int i = 0; i < kSmplMaxPoints; ++i) map.src[i] = i < c->n_points ? c->point_map[i] : 0;
-  auto points_k = &smpl_points_kernel;
-  const size_t n = (size_t)B * c->n_points * 3 * T;
-  MDM_LAUNCH(points_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)allj, (const float*)delta, mask, out, (int)B, (int)T,
-             (int)c->n_points, p.NA, (int)c->root_point, map);
-  return rt_launch_status();
-}
-
-}  // extern "C"
-
-namespace {
-
-struct EvalPlan {
-  int T1, T2;                         // frames after the first / second convolution
-  size_t motion, text;                // workspace extents, floats
-};
-
-int eval_check_gru(const std::string& f, const char* which, const mdm_eval_gru_t& g, int in_dim) {
-  const std::string w = f + which;
-  if (g.hidden <= 0 || g.hidden % 256 != 0 || g.hidden > 1024)
-    return fail(MDM_EUNSUPPORTED, w + ".hidden must be 256, 512, 768 or 1024 (the step kernel's 8 x 32-deep k split and the LayerNorm rows)");
-  if (g.in_dim != in_dim) return fail(MDM_EINVAL, w + ".in_dim must equal the width of what feeds it (" + std::to_string(in_dim) + ")");
-  if (g.out <= 0 || g.out % 4 != 0) return fail(MDM_EUNSUPPORTED, w + ".out must be a positive multiple of 4");
-  const float* ptrs[] = {g.in_w, g.in_b, g.w_ih, g.b_ih, g.w_hh, g.b_hh, g.h0, g.o1_w, g.o1_b, g.ln_g, g.ln_b, g.o2_w, g.o2_b};
-  for (const float* q : ptrs) {
-    if (q == nullptr) return fail(MDM_EINVAL, w + ": null weight pointer");
-    if ((reinterpret_cast<uintptr_t>(q) & 15) != 0) return fail(MDM_EINVAL, w + ": weight pointers must be 16-byte aligned");
-  }
-  return 0;
-}
-
-// Validation shared by the three mdm_eval_* entry points; 0 or a negative code with the message set.  T or L may be 0 (unused side).
-int eval_plan(const char* fn, const mdm_eval_model_t* m, int B, int T, int L, EvalPlan& p) {
-  const std::string f = std::string(fn) + ": ";
-  if (m == nullptr) return fail(MDM_EINVAL, f + "null model");
-  if (B <= 0 || T < 0 || L < 0) return fail(MDM_EINVAL, f + "need B >= 1, T >= 0 and L >= 0");
-  if (m->unit_length != 4) return fail(MDM_EUNSUPPORTED, f + "unit_length must be 4 (two stride-2 convolutions)");
-  if (m->dim_pose < 5) return fail(MDM_EINVAL, f + "dim_pose must be at least 5 (the last 4 features are not read)");
-  if (m->conv_hidden <= 0 || m->conv_hidden % 4 || m->latent <= 0 || m->latent % 4)
-    return fail(MDM_EUNSUPPORTED, f + "conv_hidden and latent must be positive multiples of 4");
-  if (m->word <= 0 || m->word % 4 || m->pos <= 0) return fail(MDM_EUNSUPPORTED, f + "word must be a positive multiple of 4 and pos positive");
-  if (int rc = eval_check_gru(f, "motion", m->motion, m->latent)) return rc;
-  if (int rc = eval_check_gru(f, "text", m->text, m->word)) return rc;
-  const float* ptrs[] = {m->conv1_w, m->conv1_b, m->conv2_w, m->conv2_b, m->out_w, m->out_b, m->pos_w, m->pos_b};
-  for (const float* q : ptrs) {
-    if (q == nullptr) return fail(MDM_EINVAL, f + "null weight pointer");
-    if ((reinterpret_cast<uintptr_t>(q) & 15) != 0) return fail(MDM_EINVAL, f + "weight pointers must be 16-byte aligned");
-  }
-  if (T != 0 && T < 4) return fail(MDM_EINVAL, f + "T must be at least 4 frames (one movement step)");
-  if (T > (1 << 16) || L > (1 << 16)) return fail(MDM_EUNSUPPORTED, f + "at most 65536 frames / words");
-  const int64_t Hm = m->motion.hidden, Ht = m->text.hidden;
-  p.T1 = T / 2;                       // floor((T + 2 - 4) / 2) + 1
-  p.T2 = p.T1 / 2;
-  const int64_t mo = (int64_t)B * ((int64_t)p.T1 * m->conv_hidden + (int64_t)p.T2 * (2 * m->latent + 7 * Hm)) + 5 * (int64_t)B * Hm;
-  const int64_t te = (int64_t)B * L * (m->word + 7 * Ht) + 5 * (int64_t)B * Ht;
-  // (row counts and offsets inside the GEMMs are 32-bit)
-  if ((int64_t)B * std::max(p.T2, L) * 6 * std::max(Hm, Ht) >= (1ll << 31) || (int64_t)B * std::max(T, L) * std::max(m->dim_pose, m->word) >= (1ll << 31))
-    return fail(MDM_EUNSUPPORTED, f + "batch too large for one call: chunk the rows (a row's result does not depend on the batch)");
-  p.motion = T ? (size_t)mo : 0;
-  p.text = L ? (size_t)te : 0;
-  return 0;
-}
-
-// (launch_gemm_f32_t<false>: the exact-fp32 arithmetic only -- the split-precision forms of these GEMMs are never instantiated)
-int eval_linear(const float* in, const float* w, const float* b, float* out, int M, int N, int K, hipStream_t s) {
-  RowMajorLoader al{in, K, M, K};
-  RowMajorLoader bl{w, K, N, K};
-  LeakyEpilogue ep{out, b, N, 0};
-  launch_gemm_f32_t<false>(al, bl, ep, M, N, K, s, 0);
-  return rt_launch_status();
-}
-
-// x [B Tp][g.hidden] (input_emb's output) -> out [B][g.out]: the input projections of all steps, the recurrence, output_net
-int eval_gru_encode(const mdm_eval_gru_t& g, const float* emb, const int32_t* lens, int len_div, int max_len, float* gi, float* h,
-                    float* o1, float* out, int B, int Tp, hipStream_t s) {
-  const int H = g.hidden;
-  if (int rc = eval_linear(emb, g.w_ih, g.b_ih, gi, B * Tp, 6 * H, H, s)) return rc;
-  float* hb[2] = {h, h + (size_t)B * 2 * H};
-  auto init_k = &gru_init_kernel;
-  MDM_LAUNCH(init_k, dim3((unsigned)(((size_t)B * 2 * H + 255) / 256)), dim3(256), 0, s, hb[0], g.h0, B, H);
-  if (int rc = rt_launch_status()) return rc;
-  int steps = max_len > 0 ? std::min(max_len / len_div, Tp) : Tp;
-  auto step_k = &gru_step_kernel;
-  const dim3 grid(H / 32, (B + 31) / 32, 2);
-  for (int st = 0; st < steps; ++st) {
-    MDM_LAUNCH(step_k, grid, dim3(GRU_THREADS), 0, s, (const float*)gi, g.w_hh, g.b_hh, (const float*)hb[st & 1], hb[(st + 1) & 1], lens,
-               len_div, B, Tp, H, st);
-    if (int rc = rt_launch_status()) return rc;
-  }
-  const float* hl = hb[steps & 1];                      // [B][2H] = cat(gru_last[0], gru_last[1])
-  if (int rc = eval_linear(hl, g.o1_w, g.o1_b, o1, B, H, 2 * H, s)) return rc;
-  if (int rc = launch_layernorm(nullptr, o1, g.ln_g, g.ln_b, B, H, nullptr, nullptr, s)) return rc;
-  LeakyRowLoader al{o1, H, B, H};
-  RowMajorLoader bl{g.o2_w, H, g.out, H};
-  LeakyEpilogue ep{out, g.o2_b, g.out, 0};
-  launch_gemm_f32_t<false>(al, bl, ep, B, g.out, H, s, 0);
-  return rt_launch_status();
-}
-
-float* eval_ws(void* ws) { return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15); }
-
-}  // namespace
-
-extern "C" {
-
-size_t mdm_eval_workspace_bytes(const mdm_eval_model_t* model, int32_t B, int32_t T, int32_t L) {
-  EvalPlan p;
-  if (eval_plan("mdm_eval_workspace_bytes", model, B, T, L, p) != 0) return 0;
-  return std::max(p.motion, p.text) * sizeof(float) + 64;
-}
-
-int mdm_eval_motion_embeddings(const mdm_eval_model_t* m, const float* motions, const int32_t* lens, float* out, int32_t B, int32_t T,
-                               int32_t max_len, void* ws, size_t ws_bytes, void* stream) {
-  const char* fn = "mdm_eval_motion_embeddings";
-  EvalPlan p;
-  if (int rc = eval_plan(fn, m, B, T, 0, p)) return rc;
-  if (T < 4) return fail(MDM_EINVAL, "mdm_eval_motion_embeddings: T must be at least 4 frames (one movement step)");
-  if (!motions || !lens || !out || !ws) return fail(MDM_EINVAL, "mdm_eval_motion_embeddings: null motions, lens, out or workspace");
-  if (max_len < 0) return fail(MDM_EINVAL, "mdm_eval_motion_embeddings: max_len must be >= 0");
-  if (ws_bytes < p.motion * sizeof(float) + 64) return fail(MDM_ENOSPC, "mdm_eval_motion_embeddings: workspace too small (mdm_eval_workspace_bytes)");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  ChainGuard chain_guard(stream);
-  const int Hm = m->motion.hidden, C = m->dim_pose - 4, CH = m->conv_hidden, LAT = m->latent;
-  float* c1 = eval_ws(ws);
-  float* c2 = c1 + (size_t)B * p.T1 * CH;
-  float* mv = c2 + (size_t)B * p.T2 * LAT;
-  float* emb = mv + (size_t)B * p.T2 * LAT;
-  float* gi = emb + (size_t)B * p.T2 * Hm;
-  float* h = gi + (size_t)B * p.T2 * 6 * Hm;
-  float* o1 = h + (size_t)4 * B * Hm;
-  {
-    Conv4GatherLoader al{motions, T, p.T1, m->dim_pose, C, B * p.T1};
-    RowMajorLoader bl{m->conv1_w, 4 * C, CH, 4 * C};
-    LeakyEpilogue ep{c1, m->conv1_b, CH, 1};
-    launch_gemm_f32_t<false>(al, bl, ep, B * p.T1, CH, 4 * C, s, 0);
-    if (int rc = rt_launch_status()) return rc;
-  }
-  {
-    Conv4GatherLoader al{c1, p.T1, p.T2, CH, CH, B * p.T2};
-    RowMajorLoader bl{m->conv2_w, 4 * CH, LAT, 4 * CH};
-    LeakyEpilogue ep{c2, m->conv2_b, LAT, 1};
-    launch_gemm_f32_t<false>(al, bl, ep, B * p.T2, LAT, 4 * CH, s, 0);
-    if (int rc = rt_launch_status()) return rc;
-  }
-  if (int rc = eval_linear(c2, m->out_w, m->out_b, mv, B * p.T2, LAT, LAT, s)) return rc;
-  if (int rc = eval_linear(mv, m->motion.in_w, m->motion.in_b, emb, B * p.T2, Hm, LAT, s)) return rc;
-  return eval_gru_encode(m->motion, emb, lens, m->unit_length, max_len > 0 ? max_len : T, gi, h, o1, out, B, p.T2, s);
-}
-
-int mdm_eval_text_embeddings(const mdm_eval_model_t* m, const float* word_embs, const float* pos_ohot, const int32_t* cap_lens,
-                             float* out, int32_t B, int32_t L, int32_t max_len, void* ws, size_t ws_bytes, void* stream) {
-  const char* fn = "mdm_eval_text_embeddings";
-  EvalPlan p;
-  if (int rc = eval_plan(fn, m, B, 0, L, p)) return rc;
-  if (L < 1) return fail(MDM_EINVAL, "mdm_eval_text_embeddings: L must be at least 1 word");
-  if (!word_embs || !pos_ohot || !cap_lens || !out || !ws) return fail(MDM_EINVAL, "mdm_eval_text_embeddings: null input, out or workspace");
-  if ((reinterpret_cast<uintptr_t>(word_embs) & 15) != 0) return fail(MDM_EINVAL, "mdm_eval_text_embeddings: word_embs must be 16-byte aligned");
-  if (max_len < 0) return fail(MDM_EINVAL, "mdm_eval_text_embeddings: max_len must be >= 0");
-  if (ws_bytes < p.text * sizeof(float) + 64) return fail(MDM_ENOSPC, "mdm_eval_text_embeddings: workspace too small (mdm_eval_workspace_bytes)");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  ChainGuard chain_guard(stream);
-  const int Ht = m->text.hidden, W = m->word;
-  float* inp = eval_ws(ws);
-  float* emb = inp + (size_t)B * L * W;
-  float* gi = emb + (size_t)B * L * Ht;
-  float* h = gi + (size_t)B * L * 6 * Ht;
-  float* o1 = h + (size_t)4 * B * Ht;
-  {   // inputs = word_embs + pos_emb(pos_ohot)   (modules.py:338-339)
-    ScalarRowLoader al{pos_ohot, m->pos, B * L, m->pos};
-    ScalarRowLoader bl{m->pos_w, m->pos, W, m->pos};
-    LinearEpilogue ep{inp, m->pos_b, word_embs, W, ACT_NONE, 0, 1.f, nullptr, nullptr};
-    launch_gemm_f32_t<false>(al, bl, ep, B * L, W, m->pos, s, 0);
-    if (int rc = rt_launch_status()) return rc;
-  }
-  if (int rc = eval_linear(inp, m->text.in_w, m->text.in_b, emb, B * L, Ht, W, s)) return rc;
-  return eval_gru_encode(m->text, emb, cap_lens, 1, max_len > 0 ? max_len : L, gi, h, o1, out, B, L, s);
-}
-
-}  // extern "C"
-
-namespace {
-
-// Validation shared by mdm_text_workspace_bytes and mdm_text_encode; 0 or a negative code with the message set (it names the field)
-int text_plan(const char* fn, const mdm_text_model_t* m, int B, int L, size_t& floats) {
-  const std::string f = std::string(fn) + ": ";
-  if (m == nullptr) return fail(MDM_EINVAL, f + "null model");
-  if (B < 1) return fail(MDM_EINVAL, f + "B must be at least 1");
-  if (L < 1) return fail(MDM_EINVAL, f + "L must be at least 1 word piece");
-  if (L > TXT_MAX_L) return fail(MDM_EUNSUPPORTED, f + "L must be at most 128 word pieces (the attention kernel keeps 4 key tiles of 32)");
-  if (m->max_pos < 1) return fail(MDM_EINVAL, f + "max_pos must be at least 1");
-  if (L > m->max_pos) return fail(MDM_EINVAL, f + "L exceeds max_pos, the rows of the position table (" + std::to_string(m->max_pos) + ")");
-  if (m->n_heads < 1 || m->dim != TXT_HD * m->n_heads) return fail(MDM_EUNSUPPORTED, f + "dim must equal 64 * n_heads (heads of 64)");
-  if (m->dim > TXT_MAX_DIM) return fail(MDM_EUNSUPPORTED, f + "dim must be at most 1024 (the LayerNorm rows)");
-  if (m->hidden < 4 || m->hidden % 4 != 0) return fail(MDM_EUNSUPPORTED, f + "hidden must be a positive multiple of 4");
-  if (m->n_layers < 1 || m->n_layers > 16) return fail(MDM_EUNSUPPORTED, f + "n_layers must be between 1 and 16");
-  if (m->vocab < 1) return fail(MDM_EINVAL, f + "vocab must be at least 1");
-  if (!(m->ln_eps >= 0.f)) return fail(MDM_EINVAL, f + "ln_eps must be >= 0");
-  auto check = [&](const float* q, const std::string& name) {
-    if (q == nullptr) return fail(MDM_EINVAL, f + "null weight pointer " + name);
-    if ((reinterpret_cast<uintptr_t>(q) & 15) != 0) return fail(MDM_EINVAL, f + "weight pointer " + name + " must be 16-byte aligned");
-    return 0;
-  };
-  const float* top[] = {m->word_emb, m->pos_emb, m->emb_ln_g, m->emb_ln_b};
-  const char* top_names[] = {"word_emb", "pos_emb", "emb_ln_g", "emb_ln_b"};
-  for (int i = 0; i < 4; ++i)
-    if (int rc = check(top[i], top_names[i])) return rc;
-  if (m->layers == nullptr) return fail(MDM_EINVAL, f + "null layers");
-  static const char* layer_names[] = {"qkv_w", "qkv_b", "out_w", "out_b", "sa_ln_g", "sa_ln_b", "lin1_w", "lin1_b", "lin2_w", "lin2_b", "out_ln_g", "out_ln_b"};
-  for (int l = 0; l < m->n_layers; ++l) {
-    const mdm_text_layer_t& y = m->layers[l];
-    const float* ptrs[] = {y.qkv_w, y.qkv_b, y.out_w, y.out_b, y.sa_ln_g, y.sa_ln_b, y.lin1_w, y.lin1_b, y.lin2_w, y.lin2_b, y.out_ln_g, y.out_ln_b};
-    for (int i = 0; i < 12; ++i)
-      if (int rc = check(ptrs[i], "layers[" + std::to_string(l) + "]." + layer_names[i])) return rc;
-  }
-  // (row counts and offsets inside the GEMMs are 32-bit)
-  if ((int64_t)B * L * std::max<int64_t>(3 * (int64_t)m->dim, m->hidden) >= (1ll << 31))
-    return fail(MDM_EUNSUPPORTED, f + "B too large for one call: chunk the prompts (a row's result does not depend on the batch)");
-  floats = (size_t)B * L * (5 * (size_t)m->dim + m->hidden);
-  return 0;
-}
-
-// One dense layer of the encoder on gemm_f32.h's exact-fp32 kernel.  launch_gemm_f32_t sends an output of fewer than 64 x 64 x 4
-// elements to its 128-row tiles: a one-prompt call's out_lin and lin2 (12 x 768) would be 6 workgroups walking K = 768 / 3072 alone,
-// 138 us a launch and 80 % of the call (profiles/r14a_text_encoder.md).  Those go to the 64-row tiles here -- twice the workgroups;
-// both tile shapes sum k in one order, so a row keeps its bits whichever one a batch size selects.
-int text_linear(const float* in, const float* w, const float* bias, const float* res, float* out, int M, int N, int K, int act,
-                hipStream_t s) {
-  if ((size_t)M * N >= 64 * 64 * 4) return launch_linear(nullptr, in, K, w, bias, res, out, M, N, K, act, 0, 1.f, s);
-  RowMajorLoader al{in, K, M, K};
-  RowMajorLoader bl{w, K, N, K};
-  LinearEpilogue ep{out, bias, res, N, act, 0, 1.f, nullptr, nullptr};
-  const int tm = (M + 63) / 64, tn = (N + 63) / 64;
-  auto kfn = &gemm_f32_kernel<RowMajorLoader, RowMajorLoader, LinearEpilogue, 64, false, 1>;
-  MDM_LAUNCH(kfn, dim3(tm * tn), dim3(GEMM_THREADS), gemm_f32_lds_total(64, false), s, al, bl, ep, M, N, K, tn, 0);
-  return rt_launch_status();
-}
-
-int text_ln(TextLnArgs a, hipStream_t s) {
-  auto k = &text_ln_kernel;
-  MDM_LAUNCH(k, dim3((unsigned)((a.B * a.L + 3) / 4)), dim3(256), 0, s, a);
-  return rt_launch_status();
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t mdm_text_workspace_bytes(const mdm_text_model_t* model, int32_t B, int32_t L) {
-  size_t floats = 0;
-  if (text_plan("mdm_text_workspace_bytes", model, B, L, floats) != 0) return 0;
-  return floats * sizeof(float) + 64;
-}
-
-int mdm_text_encode(const mdm_text_model_t* m, const int32_t* ids, const int32_t* lens, float* out, int32_t B, int32_t L,
-                    int32_t token_major, void* ws, size_t ws_bytes, void* stream) {
-  size_t floats = 0;
-  if (int rc = text_plan("mdm_text_encode", m, B, L, floats)) return rc;
-  if (!ids || !lens || !out || !ws) return fail(MDM_EINVAL, "mdm_text_encode: null ids_dev, lens_dev, out_dev or workspace_dev");
-  if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) return fail(MDM_EINVAL, "mdm_text_encode: out_dev must be 16-byte aligned");
-  if (ws_bytes < floats * sizeof(float) + 64) return fail(MDM_ENOSPC, "mdm_text_encode: workspace_bytes too small (mdm_text_workspace_bytes)");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  ChainGuard chain_guard(stream);
-  const int D = m->dim, H = m->n_heads, FF = m->hidden, M = B * L;
-  float* x = eval_ws(ws);                      // [M][D] the token rows (residual stream)
-  float* qkv = x + (size_t)M * D;              // [M][3D]
-  float* ctx = qkv + (size_t)M * 3 * D;        // [M][D]
-  float* ffn = ctx + (size_t)M * D;            // [M][FF]
-  TextLnArgs ln{nullptr, ids, m->word_emb, m->pos_emb, m->emb_ln_g, m->emb_ln_b, lens, x, B, L, D, m->vocab, m->ln_eps, 0};
-  if (int rc = text_ln(ln, s)) return rc;
-  ln.ids = nullptr;
-  ln.in = x;
-  auto attn_k = &text_attn_kernel<false>;
-  const int nqt = (L + 31) / 32;
-  for (int l = 0; l < m->n_layers; ++l) {
-    const mdm_text_layer_t& y = m->layers[l];
-    const bool last = l + 1 == m->n_layers;
-    if (int rc = text_linear(x, y.qkv_w, y.qkv_b, nullptr, qkv, M, 3 * D, D, ACT_NONE, s)) return rc;
-    MDM_LAUNCH(attn_k, dim3((unsigned)(B * H * nqt)), dim3(64), text_attn_lds_bytes(L), s, (const float*)qkv, lens, ctx, (int)L, D, H);
-    if (int rc = rt_launch_status()) return rc;
-    if (int rc = text_linear(ctx, y.out_w, y.out_b, x, x, M, D, D, ACT_NONE, s)) return rc;    // + x, in place
-    ln.gamma = y.sa_ln_g; ln.beta = y.sa_ln_b; ln.out = x; ln.token_major = 0;
-    if (int rc = text_ln(ln, s)) return rc;
-    if (int rc = text_linear(x, y.lin1_w, y.lin1_b, nullptr, ffn, M, FF, D, ACT_GELU, s)) return rc;
-    if (int rc = text_linear(ffn, y.lin2_w, y.lin2_b, x, x, M, D, FF, ACT_NONE, s)) return rc;   // + x, in place
-    ln.gamma = y.out_ln_g; ln.beta = y.out_ln_b; ln.out = last ? out : x; ln.token_major = last ? (token_major != 0) : 0;
-    if (int rc = text_ln(ln, s)) return rc;
-  }
-  return MDM_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// Validation shared by mdm_clip_text_workspace_bytes and mdm_clip_text_encode; 0 or a negative code with the message set (it names the field)
-int clip_text_plan(const char* fn, const mdm_clip_text_model_t* m, int B, int L, size_t& floats) {
-  const std::string f = std::string(fn) + ": ";
-  if (m == nullptr) return fail(MDM_EINVAL, f + "null model");
-  if (B < 1) return fail(MDM_EINVAL, f + "B must be at least 1");
-  if (L < 1) return fail(MDM_EINVAL, f + "L must be at least 1 token");
-  if (L > TXT_MAX_L) return fail(MDM_EUNSUPPORTED, f + "L must be at most 128 tokens (the attention kernel keeps 4 key tiles of 32)");
-  if (m->max_pos < 1) return fail(MDM_EINVAL, f + "max_pos must be at least 1");
-  if (L > m->max_pos) return fail(MDM_EINVAL, f + "L exceeds max_pos, the rows of the position table (" + std::to_string(m->max_pos) + ")");
-  if (m->n_heads < 1 || m->dim != TXT_HD * m->n_heads) return fail(MDM_EUNSUPPORTED, f + "dim must equal 64 * n_heads (heads of 64)");
-  if (m->dim > TXT_MAX_DIM) return fail(MDM_EUNSUPPORTED, f + "dim must be at most 1024 (the LayerNorm rows)");
-  if (m->mlp < 4 || m->mlp % 4 != 0) return fail(MDM_EUNSUPPORTED, f + "mlp must be a positive multiple of 4");
-  if (m->embed < 4 || m->embed % 4 != 0) return fail(MDM_EUNSUPPORTED, f + "embed must be a positive multiple of 4");
-  if (m->n_layers < 1 || m->n_layers > 32) return fail(MDM_EUNSUPPORTED, f + "n_layers must be between 1 and 32");
-  if (m->vocab < 1) return fail(MDM_EINVAL, f + "vocab must be at least 1");
-  auto check = [&](const float* q, const std::string& name) {
-    if (q == nullptr) return fail(MDM_EINVAL, f + "null weight pointer " + name);
-    if ((reinterpret_cast<uintptr_t>(q) & 15) != 0) return fail(MDM_EINVAL, f + "weight pointer " + name + " must be 16-byte aligned");
-    return 0;
-  };
-  const float* top[] = {m->tok_emb, m->pos_emb, m->lnf_g, m->lnf_b, m->text_proj};
-  const char* top_names[] = {"tok_emb", "pos_emb", "lnf_g", "lnf_b", "text_proj"};
-  for (int i = 0; i < 5; ++i)
-    if (int rc = check(top[i], top_names[i])) return rc;
-  if (m->layers == nullptr) return fail(MDM_EINVAL, f + "null layers");
-  static const char* layer_names[] = {"ln1_g", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_g", "ln2_b", "fc_w", "fc_b", "proj_w", "proj_b"};
-  for (int l = 0; l < m->n_layers; ++l) {
-    const mdm_clip_text_layer_t& y = m->layers[l];
-    const float* ptrs[] = {y.ln1_g, y.ln1_b, y.qkv_w, y.qkv_b, y.out_w, y.out_b, y.ln2_g, y.ln2_b, y.fc_w, y.fc_b, y.proj_w, y.proj_b};
-    for (int i = 0; i < 12; ++i)
-      if (int rc = check(ptrs[i], "layers[" + std::to_string(l) + "]." + layer_names[i])) return rc;
-  }
-  // (row counts and offsets inside the GEMMs are 32-bit)
-  if ((int64_t)B * L * std::max<int64_t>(3 * (int64_t)m->dim, m->mlp) >= (1ll << 31) || (int64_t)B * m->embed >= (1ll << 31))
-    return fail(MDM_EUNSUPPORTED, f + "B too large for one call: chunk the prompts (a row's result does not depend on the batch)");
-  floats = (size_t)B * L * (6 * (size_t)m->dim + m->mlp) + (size_t)B * m->dim;
-  return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t mdm_clip_text_workspace_bytes(const mdm_clip_text_model_t* model, int32_t B, int32_t L) {
-  size_t floats = 0;
-  if (clip_text_plan("mdm_clip_text_workspace_bytes", model, B, L, floats) != 0) return 0;
-  return floats * sizeof(float) + 64;
-}
-
-int mdm_clip_text_encode(const mdm_clip_text_model_t* m, const int32_t* ids, const int32_t* lens, float* out, int32_t B, int32_t L,
-                         void* ws, size_t ws_bytes, void* stream) {
-  size_t floats = 0;
-  if (int rc = clip_text_plan("mdm_clip_text_encode", m, B, L, floats)) return rc;
-  if (!ids || !lens || !out || !ws) return fail(MDM_EINVAL, "mdm_clip_text_encode: null ids_dev, lens_dev, out_dev or workspace_dev");
-  if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) return fail(MDM_EINVAL, "mdm_clip_text_encode: out_dev must be 16-byte aligned");
-  if (ws_bytes < floats * sizeof(float) + 64) return fail(MDM_ENOSPC, "mdm_clip_text_encode: workspace_bytes too small (mdm_clip_text_workspace_bytes)");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  ChainGuard chain_guard(stream);
-  const int D = m->dim, H = m->n_heads, FF = m->mlp, M = B * L;
-  float* x = eval_ws(ws);                      // [M][D] the residual stream
-  float* xn = x + (size_t)M * D;               // [M][D] ln_1(x) / ln_2(x)
-  float* qkv = xn + (size_t)M * D;             // [M][3D]
-  float* ctx = qkv + (size_t)M * 3 * D;        // [M][D]
-  float* ffn = ctx + (size_t)M * D;            // [M][FF]
-  float* eot = ffn + (size_t)M * FF;           // [B][D] ln_final of the EOT rows
-  auto embed_k = &clip_embed_kernel;
-  MDM_LAUNCH(embed_k, dim3((unsigned)((M * (D / 4) + 255) / 256)), dim3(256), 0, s, ids, lens, m->tok_emb, m->pos_emb, x, (int)B, (int)L, D,
-             (int)m->vocab);
-  if (int rc = rt_launch_status()) return rc;
-  TextLnArgs ln{x, nullptr, nullptr, nullptr, nullptr, nullptr, lens, xn, B, L, D, 0, CLIP_LN_EPS, 0};
-  auto attn_k = &text_attn_kernel<true>;
-  const int nqt = (L + 31) / 32;
-  for (int l = 0; l < m->n_layers; ++l) {
-    const mdm_clip_text_layer_t& y = m->layers[l];
-    ln.gamma = y.ln1_g; ln.beta = y.ln1_b;
-    if (int rc = text_ln(ln, s)) return rc;
-    if (int rc = text_linear(xn, y.qkv_w, y.qkv_b, nullptr, qkv, M, 3 * D, D, ACT_NONE, s)) return rc;
-    MDM_LAUNCH(attn_k, dim3((unsigned)(B * H * nqt)), dim3(64), text_attn_lds_bytes(L), s, (const float*)qkv, lens, ctx, (int)L, D, H);
-    if (int rc = rt_launch_status()) return rc;
-    if (int rc = text_linear(ctx, y.out_w, y.out_b, x, x, M, D, D, ACT_NONE, s)) return rc;      // + x, in place
-    ln.gamma = y.ln2_g; ln.beta = y.ln2_b;
-    if (int rc = text_ln(ln, s)) return rc;
-    if (int rc = text_linear(xn, y.fc_w, y.fc_b, nullptr, ffn, M, FF, D, ACT_QGELU, s)) return rc;
-    if (int rc = text_linear(ffn, y.proj_w, y.proj_b, x, x, M, D, FF, ACT_NONE, s)) return rc;   // + x, in place
-  }
-  auto eot_k = &clip_eot_ln_kernel;
-  MDM_LAUNCH(eot_k, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, (const float*)x, lens, m->lnf_g, m->lnf_b, eot, (int)B, (int)L, D);
-  if (int rc = rt_launch_status()) return rc;
-  return text_linear(eot, m->text_proj, nullptr, nullptr, out, B, m->embed, D, ACT_NONE, s);
-}
-
-}  // extern "C"
-
-namespace {
-
-struct StgcnPlan {
-  int Cp;                                    // the input's channels rounded up to a multiple of 4
-  int Tin[MDM_STGCN_MAX_BLOCKS + 1];         // frames in front of block b; [n_blocks] = behind the last one
-  size_t buf;                                // floats per workspace buffer (three of them)
-};
-
-// Validation shared by mdm_stgcn_workspace_bytes and mdm_stgcn_forward; 0 or a negative code with the message set (it names the field)
-int stgcn_plan(const char* fn, const mdm_stgcn_model_t* m, int N, int T, StgcnPlan& p) {
-  const std::string f = std::string(fn) + ": ";
-  if (m == nullptr) return fail(MDM_EINVAL, f + "null model");
-  if (N < 1) return fail(MDM_EINVAL, f + "N must be at least 1");
-  if (T < 1) return fail(MDM_EINVAL, f + "T must be at least 1 frame");
-  if (T > (1 << 16)) return fail(MDM_EUNSUPPORTED, f + "T must be at most 65536 frames");
-  if (m->n_blocks < 1 || m->n_blocks > MDM_STGCN_MAX_BLOCKS) return fail(MDM_EUNSUPPORTED, f + "n_blocks must be between 1 and 16");
-  if (m->V < 1 || m->V > 64) return fail(MDM_EUNSUPPORTED, f + "V must be between 1 and 64 nodes");
-  if (m->K < 1 || m->K > 8) return fail(MDM_EUNSUPPORTED, f + "K must be between 1 and 8 graph kernels");
-  if (m->num_class < 1) return fail(MDM_EINVAL, f + "num_class must be at least 1");
-  if (m->blocks == nullptr) return fail(MDM_EINVAL, f + "null blocks");
-  auto check = [&](const void* q, const std::string& name) {
-    if (q == nullptr) return fail(MDM_EINVAL, f + "null weight pointer " + name);
-    if ((reinterpret_cast<uintptr_t>(q) & 15) != 0) return fail(MDM_EINVAL, f + "weight pointer " + name + " must be 16-byte aligned");
-    return 0;
-  };
-  const void* top[] = {m->in_scale, m->in_shift, m->fcn_w, m->fcn_b};
-  const char* top_names[] = {"in_scale", "in_shift", "fcn_w", "fcn_b"};
-  for (int i = 0; i < 4; ++i)
-    if (int rc = check(top[i], top_names[i])) return rc;
-  if (m->blocks[0].c_in < 1) return fail(MDM_EINVAL, f + "blocks[0].c_in must be at least 1 channel");
-  p.Cp = (m->blocks[0].c_in + 3) & ~3;
-  int64_t rows = (int64_t)N * T * m->V, widest = rows * p.Cp;
-  p.Tin[0] = T;
-  int c_prev = p.Cp;
-  static const char* names[] = {"gcn_w", "gcn_scale", "gcn_shift", "nbr_idx", "nbr_w", "nbr_cnt", "tcn_w", "tcn_scale", "tcn_shift",
-                                "res_w", "res_scale", "res_shift"};
-  for (int b = 0; b < m->n_blocks; ++b) {
-    const mdm_stgcn_block_t& k = m->blocks[b];
-    const std::string w = "blocks[" + std::to_string(b) + "].";
-    if (b > 0 && k.c_in != m->blocks[b - 1].c_out) return fail(MDM_EINVAL, f + w + "c_in must equal the c_out of the block in front of it");
-    if (k.c_out < 4 || k.c_out % 4 != 0) return fail(MDM_EUNSUPPORTED, f + w + "c_out must be a positive multiple of 4");
-    if (k.stride < 1 || k.stride > 4) return fail(MDM_EUNSUPPORTED, f + w + "stride must be between 1 and 4");
-    if (k.residual < MDM_STGCN_RES_NONE || k.residual > MDM_STGCN_RES_CONV) return fail(MDM_EINVAL, f + w + "residual must be one of MDM_STGCN_RES_*");
-    if (k.residual == MDM_STGCN_RES_IDENTITY && (c_prev != k.c_out || k.stride != 1))
-      return fail(MDM_EINVAL, f + w + "an identity residual needs c_in == c_out and stride 1");
-    const void* ptrs[] = {k.gcn_w, k.gcn_scale, k.gcn_shift, k.nbr_idx, k.nbr_w, k.nbr_cnt, k.tcn_w, k.tcn_scale, k.tcn_shift,
-                          k.res_w, k.res_scale, k.res_shift};
-    for (int i = 0; i < (k.residual == MDM_STGCN_RES_CONV ? 12 : 9); ++i)
-      if (int rc = check(ptrs[i], w + names[i])) return rc;
-    widest = std::max(widest, rows * k.c_out);      // the graph convolution's output: the block's input rows
-    p.Tin[b + 1] = (p.Tin[b] - 1) / k.stride + 1;
-    rows = (int64_t)N * p.Tin[b + 1] * m->V;
-    c_prev = k.c_out;
-  }
-  if (c_prev > STGCN_MAX_POOL_C) return fail(MDM_EUNSUPPORTED, f + "the last block's c_out must be at most 1024 (the pooling kernel's row)");
-  // (row counts and offsets inside the GEMMs are 32-bit)
-  if (widest >= (1ll << 31)) return fail(MDM_EUNSUPPORTED, f + "N too large for one call: chunk the samples (a sample's result does not depend on the batch)");
-  p.buf = (size_t)widest;
-  return 0;
-}
-
-// One GEMM of the net: always the 64-row tile (launch_gemm_f32_t's size rule would let the batch choose the tile shape)
-template <class AL>
-int stgcn_gemm(const AL& al, const float* w, const StgcnEpilogue& ep, int M, int N, int K, hipStream_t s) {
-  RowMajorLoader bl{w, K, N, K};
-  const int tm = (M + 63) / 64, tn = (N + 63) / 64;
-  auto kfn = &gemm_f32_kernel<AL, RowMajorLoader, StgcnEpilogue, 64, false, 1>;
-  MDM_LAUNCH(kfn, dim3(tm * tn), dim3(GEMM_THREADS), gemm_f32_lds_total(64, false), s, al, bl, ep, M, N, K, tn, 0);
-  return rt_launch_status();
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t mdm_stgcn_workspace_bytes(const mdm_stgcn_model_t* model, int32_t N, int32_t T) {
-  StgcnPlan p;
-  if (stgcn_plan("mdm_stgcn_workspace_bytes", model, N, T, p) != 0) return 0;
-  return 3 * p.buf * sizeof(float) + 64;
-}
-
-int mdm_stgcn_forward(const mdm_stgcn_model_t* m, const float* x, float* features, float* yhat, int32_t N, int32_t T, void* ws,
-                      size_t ws_bytes, void* stream) {
-  StgcnPlan p;
-  if (int rc = stgcn_plan("mdm_stgcn_forward", m, N, T, p)) return rc;
-  if (!x || !features || !yhat || !ws) return fail(MDM_EINVAL, "mdm_stgcn_forward: null x_dev, features_dev, yhat_dev or workspace_dev");
-  if ((reinterpret_cast<uintptr_t>(features) & 15) != 0) return fail(MDM_EINVAL, "mdm_stgcn_forward: features_dev must be 16-byte aligned");
-  if (ws_bytes < 3 * p.buf * sizeof(float) + 64) return fail(MDM_ENOSPC, "mdm_stgcn_forward: workspace_bytes too small (mdm_stgcn_workspace_bytes)");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  ChainGuard chain_guard(stream);
-  const int V = m->V;
-  float* cur = eval_ws(ws);                   // the block's input  [N Tin V][c_in]
-  float* mid = cur + p.buf;                   // relu(BN(gcn))      [N Tin V][c_out]
-  float* nxt = mid + p.buf;                   // the block's output [N Tout V][c_out]
-  {
-    StgcnInputArgs a{x, m->in_scale, m->in_shift, cur, N, V, m->blocks[0].c_in, p.Cp, T};
-    auto k = &stgcn_input_kernel;
-    MDM_LAUNCH(k, dim3((unsigned)(((size_t)N * T * V * p.Cp + 255) / 256)), dim3(256), 0, s, a);
-    if (int rc = rt_launch_status()) return rc;
-  }
-  int C = p.Cp;
-  for (int b = 0; b < m->n_blocks; ++b) {
-    const mdm_stgcn_block_t& k = m->blocks[b];
-    const int Tin = p.Tin[b], Tout = p.Tin[b + 1], CO = k.c_out;
-    const int Min = N * Tin * V, Mout = N * Tout * V;
-    {
-      GraphMixLoader al{cur, k.nbr_idx, k.nbr_w, k.nbr_cnt, V, C, m->K * C, Min};
-      StgcnEpilogue ep{mid, k.gcn_scale, k.gcn_shift, nullptr, CO, V, 1};
-      if (int rc = stgcn_gemm(al, k.gcn_w, ep, Min, CO, m->K * C, s)) return rc;
-    }
-    const float* res = nullptr;
-    if (k.residual == MDM_STGCN_RES_IDENTITY) res = cur;
-    if (k.residual == MDM_STGCN_RES_CONV) {
-      StrideRowLoader al{cur, Tin, Tout, V, C, k.stride, Mout};
-      StgcnEpilogue ep{nxt, k.res_scale, k.res_shift, nullptr, CO, 1, 0};
-      if (int rc = stgcn_gemm(al, k.res_w, ep, Mout, CO, C, s)) return rc;
-      res = nxt;                              // added in place by the temporal GEMM below
-    }
-    {
-      Tap9GatherLoader al{mid, Tin, Tout, V, CO, k.stride, Mout};
-      StgcnEpilogue ep{nxt, k.tcn_scale, k.tcn_shift, res, CO, 1, 1};
-      if (int rc = stgcn_gemm(al, k.tcn_w, ep, Mout, CO, STGCN_TAPS * CO, s)) return rc;
-    }
-    std::swap(cur, nxt);
-    C = CO;
-  }
-  StgcnTailArgs a{cur, m->fcn_w, m->fcn_b, features, yhat, p.Tin[m->n_blocks] * V, C, m->num_class};
-  auto k = &stgcn_tail_kernel;
-  MDM_LAUNCH(k, dim3((unsigned)N), dim3(256), 0, s, a);
-  return rt_launch_status();
-}
-
-}  // extern "C"
-
+#include "smpl_api.h"
+#include "evaluator_api.h"
+#include "text_api.h"
+#include "stgcn_api.h"
 #include "gru_recogniser_api.h"

@@ -10,9 +10,9 @@ from os.path import join as pjoin
 
 import numpy as np
 import torch
-import torch.nn as nn
 
 from . import _native as nat
+from ._native_model import NativeModelMixin, _ParamContainer      # (_ParamContainer: text_encoder / clip_text took it from here)
 
 DIM_POS_OHOT = 15          # len(POS_enumerator), data_loaders/humanml/utils/word_vectorizer.py
 ROW_CHUNK = 128            # rows per native call: bounds the workspace (a row's result does not depend on the batch it is in)
@@ -73,30 +73,6 @@ def motion_encoder_shapes(input_size, hidden_size, output_size):
         _gru_shapes(hidden_size) + _output_net_shapes(hidden_size, output_size)
 
 
-class _ParamContainer(nn.Module):
-    """Parameters under the reference module's state-dict keys and nothing else: `load_state_dict`, `.to()`, `.eval()` and
-    `state_dict()` behave as on the reference's module; there is no forward (the wrapper runs the HIP path)."""
-
-    def __init__(self, shapes):
-        super().__init__()
-        self.shapes = list(shapes)
-        for key, shape in self.shapes:
-            mod = self
-            *path, leaf = key.split(".")
-            for name in path:
-                if name not in mod._modules:
-                    mod.add_module(name, nn.Module())
-                mod = mod._modules[name]
-            mod.register_parameter(leaf, nn.Parameter(torch.zeros(*shape), requires_grad=False))
-
-    def forward(self, *a, **k):
-        raise nat.MdmError("the evaluator's encoders are parameter containers: call EvaluatorMDMWrapper.get_co_embeddings / "
-                           "get_motion_embeddings (the HIP path); there is no eager PyTorch forward")
-
-    def version(self):
-        return tuple((p._version, p.data_ptr()) for p in self.parameters())
-
-
 def _check_widths(opt):
     """What the kernels' tiles take (include/mdm_hip.h mdm_eval_model_t), refused here, at create time."""
     for k in ("dim_motion_hidden", "dim_text_hidden"):
@@ -150,7 +126,7 @@ def _check_packed_lengths(lens, limit, what):
         raise RuntimeError(f"{what}: a length of {lens[0]} is beyond the {limit} steps of the padded input")
 
 
-class EvaluatorMDMWrapper(object):
+class EvaluatorMDMWrapper(NativeModelMixin):
     """evaluator_wrapper.py:121-187: same constructor, attributes and methods; results in the reference's (sorted) order."""
 
     def __init__(self, dataset_name, device, _native_lib=None):
@@ -184,12 +160,8 @@ class EvaluatorMDMWrapper(object):
         for enc in (self.text_encoder, self.motion_encoder, self.movement_encoder):
             enc.to(opt['device'])
             enc.eval()
-        self._prepared = None
 
     # ---- native model ----------------------------------------------------------------------------------------------------------
-    def _lib(self):
-        return self._native_lib if self._native_lib is not None else nat.load_native()
-
     def _gru_tables(self, enc, in_dim):
         sd = {k: v.detach().float() for k, v in enc.state_dict().items()}
         H = sd["hidden"].shape[-1]
@@ -205,38 +177,25 @@ class EvaluatorMDMWrapper(object):
         return t, nat.MdmEvalGru(in_dim=in_dim, hidden=H, out=sd["output_net.3.weight"].shape[0],
                                  **{k: v.data_ptr() for k, v in t.items()})
 
-    def _model(self):
-        """The prepared weight tables (concatenated GRU directions, tap-major convolution weights) and the C struct over them;
-        rebuilt when a parameter was replaced or written since."""
-        ver = (self.movement_encoder.version(), self.text_encoder.version(), self.motion_encoder.version())
-        if self._prepared is None or self._prepared[0] != ver:
-            mv = {k: v.detach().float() for k, v in self.movement_encoder.state_dict().items()}
-            tx = self.text_encoder.state_dict()
-            top = dict(conv1_w=mv["main.0.weight"].permute(0, 2, 1), conv1_b=mv["main.0.bias"],     # [out][tap][in]
-                       conv2_w=mv["main.3.weight"].permute(0, 2, 1), conv2_b=mv["main.3.bias"],
-                       out_w=mv["out_net.weight"], out_b=mv["out_net.bias"],
-                       pos_w=tx["pos_emb.weight"].detach().float(), pos_b=tx["pos_emb.bias"].detach().float())
-            top = {k: v.contiguous().clone() for k, v in top.items()}
-            o = self.opt
-            mt, mg = self._gru_tables(self.motion_encoder, o['dim_movement_latent'])
-            tt, tg = self._gru_tables(self.text_encoder, o['dim_word'])
-            model = nat.MdmEvalModel(motion=mg, text=tg, dim_pose=o['dim_pose'], conv_hidden=o['dim_movement_enc_hidden'],
-                                     latent=o['dim_movement_latent'], word=o['dim_word'], pos=o['dim_pos_ohot'],
-                                     unit_length=o['unit_length'], **{k: v.data_ptr() for k, v in top.items()})
-            self._prepared = (ver, model, (top, mt, tt))
-        return self._prepared[1]
+    def _native_version(self):
+        return (self.movement_encoder.version(), self.text_encoder.version(), self.motion_encoder.version())
 
-    def _device_check(self, lib, t):
-        emulation = not lib.path.endswith(nat.LIB_NAME)
-        if not emulation and not t.is_cuda:
-            raise nat.MdmError("the MI355X HIP path needs tensors on a cuda (ROCm) device; got " + str(t.device))
-        return torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else None
-
-    def _workspace(self, lib, model, B, T, L, dev):
-        nbytes = lib.mdm_eval_workspace_bytes(nat.C.byref(model), B, T, L)
-        if nbytes == 0:
-            lib.check(-1, "mdm_eval_workspace_bytes")
-        return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+    def _build_native(self, keep):
+        """The prepared weight tables (concatenated GRU directions, tap-major convolution weights) and the C struct over them."""
+        mv = {k: v.detach().float() for k, v in self.movement_encoder.state_dict().items()}
+        tx = self.text_encoder.state_dict()
+        top = dict(conv1_w=mv["main.0.weight"].permute(0, 2, 1), conv1_b=mv["main.0.bias"],     # [out][tap][in]
+                   conv2_w=mv["main.3.weight"].permute(0, 2, 1), conv2_b=mv["main.3.bias"],
+                   out_w=mv["out_net.weight"], out_b=mv["out_net.bias"],
+                   pos_w=tx["pos_emb.weight"].detach().float(), pos_b=tx["pos_emb.bias"].detach().float())
+        top = {k: v.contiguous().clone() for k, v in top.items()}
+        o = self.opt
+        mt, mg = self._gru_tables(self.motion_encoder, o['dim_movement_latent'])
+        tt, tg = self._gru_tables(self.text_encoder, o['dim_word'])
+        keep += [top, mt, tt]
+        return nat.MdmEvalModel(motion=mg, text=tg, dim_pose=o['dim_pose'], conv_hidden=o['dim_movement_enc_hidden'],
+                                latent=o['dim_movement_latent'], word=o['dim_word'], pos=o['dim_pos_ohot'],
+                                unit_length=o['unit_length'], **{k: v.data_ptr() for k, v in top.items()})
 
     def _check_motion(self, motions, m_lens):
         o = self.opt
@@ -256,11 +215,11 @@ class EvaluatorMDMWrapper(object):
         B, T = motions.shape[0], motions.shape[1]
         lib, model = self._lib(), self._model()
         motions = motions.contiguous()
-        stream = self._device_check(lib, motions)
+        stream = self._stream(lib, motions, "tensors")
         dev = motions.device
         out = torch.empty(B, o['dim_coemb_hidden'], dtype=torch.float32, device=dev)
         lens_dev = torch.tensor(m_lens, dtype=torch.int32).to(dev)
-        ws, nbytes = self._workspace(lib, model, min(B, ROW_CHUNK), T, 0, dev)
+        ws, nbytes = self._workspace("mdm_eval_workspace_bytes", model, min(B, ROW_CHUNK), T, 0, dev=dev)
         for b0 in range(0, B, ROW_CHUNK):
             n = min(ROW_CHUNK, B - b0)
             lib.check(lib.mdm_eval_motion_embeddings(nat.C.byref(model), motions[b0:b0 + n].data_ptr(), lens_dev[b0:b0 + n].data_ptr(),
@@ -285,11 +244,11 @@ class EvaluatorMDMWrapper(object):
         B, L = word_embs.shape[0], word_embs.shape[1]
         lib, model = self._lib(), self._model()
         word_embs, pos_ohot = word_embs.contiguous(), pos_ohot.contiguous()
-        stream = self._device_check(lib, word_embs)
+        stream = self._stream(lib, word_embs, "tensors")
         dev = word_embs.device
         out = torch.empty(B, o['dim_coemb_hidden'], dtype=torch.float32, device=dev)
         lens_dev = torch.tensor(cap_lens, dtype=torch.int32).to(dev)
-        ws, nbytes = self._workspace(lib, model, min(B, ROW_CHUNK), 0, L, dev)
+        ws, nbytes = self._workspace("mdm_eval_workspace_bytes", model, min(B, ROW_CHUNK), 0, L, dev=dev)
         for b0 in range(0, B, ROW_CHUNK):
             n = min(ROW_CHUNK, B - b0)
             lib.check(lib.mdm_eval_text_embeddings(nat.C.byref(model), word_embs[b0:b0 + n].data_ptr(), pos_ohot[b0:b0 + n].data_ptr(),

@@ -14,12 +14,13 @@ import torch
 import torch.nn as nn
 
 from . import _native as nat
+from ._native_model import NativeModelMixin
 
 ROW_CHUNK = 256            # sequences per native call: bounds the workspace (a row's result does not depend on the batch it is in)
 MID = 30                   # linear1's width
 
 
-class MotionDiscriminator(nn.Module):
+class MotionDiscriminator(NativeModelMixin, nn.Module):
     """eval/a2m/action2motion/models.py MotionDiscriminator: forward returns the logits [bs, output_size]."""
 
     def __init__(self, input_size, hidden_size, hidden_layer, device, output_size=12, use_noise=None, _native_lib=None):
@@ -35,23 +36,15 @@ class MotionDiscriminator(nn.Module):
         self.recurrent = nn.GRU(input_size, hidden_size, hidden_layer)      # a parameter container: its forward is never called
         self.linear1 = nn.Linear(hidden_size, MID)
         self.linear2 = nn.Linear(MID, output_size)
-        self._prepared = None
 
     # ---- native model --------------------------------------------------------------------------------------------------------------
-    def _lib(self):
-        return self._native_lib if self._native_lib is not None else nat.load_native()
-
-    def _version(self):
+    def _native_version(self):
         return tuple((t._version, t.data_ptr()) for t in self.parameters())
 
-    def _model(self):
+    def _build_native(self, keep):
         """The C struct over fp32, contiguous, 16-byte aligned copies of the parameters on their device (the parameters themselves
-        where they already are that); rebuilt when a parameter was replaced (load_state_dict, .to()) or written since."""
-        ver = self._version()
-        if self._prepared is not None and self._prepared[0] == ver:
-            return self._prepared[1]
+        where they already are that)."""
         dev = self.linear1.weight.device
-        keep = []
 
         def put(t):
             t = t.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -70,7 +63,6 @@ class MotionDiscriminator(nn.Module):
             y = model.layers[l]
             y.w_ih, y.w_hh = put(getattr(self.recurrent, f"weight_ih_l{l}")), put(getattr(self.recurrent, f"weight_hh_l{l}"))
             y.b_ih, y.b_hh = put(getattr(self.recurrent, f"bias_ih_l{l}")), put(getattr(self.recurrent, f"bias_hh_l{l}"))
-        self._prepared = (ver, model, keep)
         return model
 
     def run(self, motion_sequence, lengths=None, hidden_unit=None):
@@ -96,20 +88,14 @@ class MotionDiscriminator(nn.Module):
 
         lib, model = self._lib(), self._model()
         dev = self.linear1.weight.device
-        emulation = not lib.path.endswith(nat.LIB_NAME)
-        if not emulation and dev.type != "cuda":
-            raise nat.MdmError("the MI355X HIP path needs the model on a cuda (ROCm) device; got " + str(dev))
+        stream = self._stream(lib, dev, "the model")
         x = motion_sequence.detach().reshape(bs, njoints * nfeats, T).to(device=dev).float().contiguous()
         h0 = hidden_unit.detach().to(device=dev, dtype=torch.float32).contiguous()
         lens = lengths.to(device=dev, dtype=torch.int32).contiguous()
-        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
         features = torch.empty(bs, model.mid, dtype=torch.float32, device=dev)
         yhat = torch.empty(bs, model.num_class, dtype=torch.float32, device=dev)
         chunk = min(bs, ROW_CHUNK)
-        nbytes = lib.mdm_gru_cls_workspace_bytes(nat.C.byref(model), chunk, T)
-        if nbytes == 0:
-            lib.check(-1, "mdm_gru_cls_workspace_bytes")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws, nbytes = self._workspace("mdm_gru_cls_workspace_bytes", model, chunk, T, dev=dev)
         for n0 in range(0, bs, chunk):
             n = min(chunk, bs - n0)
             h0c = h0 if n == bs else h0[:, n0:n0 + n].contiguous()

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as nat
+from ._native_model import NativeModelMixin
 
 SMPL_MODEL_PATH = os.path.join("./body_models/smpl", "SMPL_NEUTRAL.pkl")     # utils/config.py:3-6, relative to the working dir
 DOWNLOAD_SCRIPT = "prepare/download_smpl_files.sh"
@@ -85,7 +86,7 @@ def load_smpl_tables(path=SMPL_MODEL_PATH):
     return np.ascontiguousarray(rest), np.ascontiguousarray(parents.astype(np.int32))
 
 
-class Rotation2xyz:
+class Rotation2xyz(NativeModelMixin):
     """model/rotation2xyz.py:10-90 with the reference's call signature.  `model_path` defaults to the reference's location; the
     file is read at the first non-'xyz' call and its tables are cached on the object."""
 
@@ -121,10 +122,8 @@ class Rotation2xyz:
         if x.dim() != 4 or x.shape[2] != 6:
             raise ValueError(f"x must be [B, joints + 1, 6, T] rot6d features, got {tuple(x.shape)}")
         rest, parents = self.tables()
-        lib = self._native_lib if self._native_lib is not None else nat.load_native()
-        emulation = not lib.path.endswith(nat.LIB_NAME)
-        if not emulation and not x.is_cuda:
-            raise nat.MdmError("the MI355X HIP path needs tensors on a cuda (ROCm) device; got " + str(x.device))
+        lib = self._lib()
+        stream = self._stream(lib, x, "tensors")
         B, NJ, _, T = x.shape
         J = rest.shape[0]
         if NJ != J + 1:
@@ -136,7 +135,6 @@ class Rotation2xyz:
                 raise ValueError(f"mask must be [B, T] = {(B, T)}, got {tuple(mask.shape)}")
             m = mask.to(device=x.device, dtype=torch.uint8).contiguous()
         out = torch.empty(B, J, 3, T, dtype=torch.float32, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream if x.is_cuda else None
         lib.check(lib.mdm_rot6d_to_smpl_joints(x.data_ptr(), m.data_ptr() if m is not None else None,
                                                rest.ctypes.data_as(nat.C.POINTER(nat.C.c_float)),
                                                parents.ctypes.data_as(nat.C.POINTER(nat.C.c_int32)),

@@ -232,10 +232,8 @@ class Rotation2xyzFull(Rotation2xyz):
         if x.dim() != 4 or x.shape[1] != rows or x.shape[2] != F:
             raise ValueError(f"x must be [B, {rows}, {F}, T] for pose_rep={pose_rep!r}, glob={bool(glob)}, "
                              f"translation={bool(translation)} on a model of {J} joints, got {tuple(x.shape)}")
-        lib = self._native_lib if self._native_lib is not None else nat.load_native()
-        emulation = not lib.path.endswith(nat.LIB_NAME)
-        if not emulation and not x.is_cuda:
-            raise nat.MdmError("the MI355X HIP path needs tensors on a cuda (ROCm) device; got " + str(x.device))
+        lib = self._lib()
+        stream = self._stream(lib, x, "tensors")
         B, T = x.shape[0], x.shape[-1]
         dev = x.device
         x = x.contiguous().float()
@@ -277,13 +275,9 @@ class Rotation2xyzFull(Rotation2xyz):
                                root_point=JOINTSTYPE_ROOT[jointstype] if joints else 0,
                                point_map=pmap.ctypes.data_as(i32p) if joints else None,
                                glob_rot_mat=grot.ctypes.data_as(f32p) if grot is not None else None, beta1=float(beta))
-        nbytes = lib.mdm_smpl_workspace_bytes(nat.C.byref(model), nat.C.byref(call), B, T)
-        if nbytes == 0:
-            lib.check(-1, "mdm_smpl_workspace_bytes")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws, nbytes = self._workspace("mdm_smpl_workspace_bytes", model, call, B, T, dev=dev)
         out = torch.empty(B, n_points if joints else V, 3, T, dtype=torch.float32, device=dev)
         rot = torch.zeros(B, T, NR, 3, 3, dtype=torch.float32, device=dev) if get_rotations_back else None
-        stream = torch.cuda.current_stream(dev).cuda_stream if x.is_cuda else None
         lib.check(lib.mdm_smpl_forward(nat.C.byref(model), nat.C.byref(call), x.data_ptr(), mk.data_ptr() if mk is not None else None,
                                        bt.data_ptr() if bt is not None else None, out.data_ptr(),
                                        rot.data_ptr() if rot is not None else None, B, T, rows, F, ws.data_ptr(), nbytes, stream),

@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as nat
+from ._native_model import NativeModelMixin
 
 ROW_CHUNK = 128            # samples per native call: bounds the workspace (a sample's result does not depend on the batch it is in)
 TEMPORAL_KERNEL = 9
@@ -173,7 +174,7 @@ def _bn_fold(bn, bias=None):
     return scale, shift
 
 
-class STGCN(nn.Module):
+class STGCN(NativeModelMixin, nn.Module):
     """eval/a2m/recognition/models/stgcn.py STGCN: same constructor, parameter / buffer names and batch contract.
     forward(batch) reads batch["output"] [N, V, in_channels, T] and sets batch["features"] (`squeeze()`d: [256] for N = 1) and
     batch["yhat"] [N, num_class]."""
@@ -213,13 +214,9 @@ class STGCN(nn.Module):
         else:
             self.edge_importance = [1] * len(self.st_gcn_networks)
         self.fcn = nn.Conv2d(blocks[-1][1], num_class, kernel_size=1)
-        self._prepared = None
 
     # ---- native model ----------------------------------------------------------------------------------------------------------
-    def _lib(self):
-        return self._native_lib if self._native_lib is not None else nat.load_native()
-
-    def _version(self):
+    def _native_version(self):
         return tuple((t._version, t.data_ptr()) for t in list(self.parameters()) + list(self.buffers()))
 
     def _neighbour_lists(self, A_b):
@@ -236,15 +233,10 @@ class STGCN(nn.Module):
                 idx[k, w, :len(vs)], wgt[k, w, :len(vs)], cnt[k, w] = vs, A_b[k, vs, w], len(vs)
         return idx, wgt, cnt
 
-    def _model(self):
+    def _build_native(self, keep):
         """The prepared tables -- A * importance as neighbour lists, the BatchNorm scale / shift pairs (fp64, rounded once), the
-        k-behind-c_out graph weights and the tap-major temporal weights -- and the C structs over them; rebuilt when a parameter or
-        buffer was replaced (load_state_dict, .to()) or written since."""
-        ver = self._version()
-        if self._prepared is not None and self._prepared[0] == ver:
-            return self._prepared[1]
+        k-behind-c_out graph weights and the tap-major temporal weights -- and the C structs over them."""
         dev = self.fcn.weight.device
-        keep = []
 
         def put(a, dtype=np.float32):
             t = torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
@@ -282,12 +274,11 @@ class STGCN(nn.Module):
                 d.res_w, d.res_scale, d.res_shift = put(rw), put(sr), put(hr)
             c_prev_p = co
         s0, h0 = _bn_fold(self.data_bn)
-        model = nat.MdmStgcnModel(blocks=blocks, in_scale=put(s0), in_shift=put(h0),
-                                  fcn_w=put(self.fcn.weight.detach().float().cpu().numpy().reshape(self.num_class, -1)),
-                                  fcn_b=put(self.fcn.bias.detach().float().cpu().numpy()),
-                                  n_blocks=len(blocks), V=V, K=K, num_class=self.num_class)
-        self._prepared = (ver, model, (keep, blocks))
-        return model
+        keep.append(blocks)
+        return nat.MdmStgcnModel(blocks=blocks, in_scale=put(s0), in_shift=put(h0),
+                                 fcn_w=put(self.fcn.weight.detach().float().cpu().numpy().reshape(self.num_class, -1)),
+                                 fcn_b=put(self.fcn.bias.detach().float().cpu().numpy()),
+                                 n_blocks=len(blocks), V=V, K=K, num_class=self.num_class)
 
     def _check(self, x):
         if self.training:
@@ -306,18 +297,11 @@ class STGCN(nn.Module):
         lib, model = self._lib(), self._model()
         dev = self.fcn.weight.device
         x = x.detach().to(device=dev, dtype=torch.float32).contiguous()
-        emulation = not lib.path.endswith(nat.LIB_NAME)
-        if not emulation and not x.is_cuda:
-            raise nat.MdmError("the MI355X HIP path needs the model on a cuda (ROCm) device; got " + str(x.device))
-        stream = torch.cuda.current_stream(dev).cuda_stream if x.is_cuda else None
+        stream = self._stream(lib, x, "the model")
         N, T = x.shape[0], x.shape[3]
         features = torch.empty(N, self.fcn.weight.shape[1], dtype=torch.float32, device=dev)
         yhat = torch.empty(N, self.num_class, dtype=torch.float32, device=dev)
-        chunk = min(N, ROW_CHUNK)
-        nbytes = lib.mdm_stgcn_workspace_bytes(nat.C.byref(model), chunk, T)
-        if nbytes == 0:
-            lib.check(-1, "mdm_stgcn_workspace_bytes")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws, nbytes = self._workspace("mdm_stgcn_workspace_bytes", model, min(N, ROW_CHUNK), T, dev=dev)
         for n0 in range(0, N, ROW_CHUNK):
             n = min(ROW_CHUNK, N - n0)
             lib.check(lib.mdm_stgcn_forward(nat.C.byref(model), x[n0:n0 + n].data_ptr(), features[n0:n0 + n].data_ptr(),

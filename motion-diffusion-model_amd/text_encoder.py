@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as nat
-from .evaluator import _ParamContainer
+from ._native_model import NativeModelMixin, _ParamContainer
 
 MAX_WORD_PIECES = 128      # include/mdm_hip.h mdm_text_encode
 HEAD_DIM = 64
@@ -55,14 +55,13 @@ def load_bert(model_path, _native_lib=None):
     return bert
 
 
-class BERT(nn.Module):
+class BERT(NativeModelMixin, nn.Module):
     """BERT_encoder.py:12-32: `.tokenizer`, `.text_model`, forward(texts) -> (last_hidden_state [B, L, dim] fp32, mask [B, L] bool)."""
 
     def __init__(self, modelpath=None, _native_lib=None):
         super().__init__()
         self._native_lib = _native_lib
         self.tokenizer = None
-        self._prepared = None
         self._ws = {}
         if modelpath is not None:
             self._init_from_dir(modelpath)
@@ -111,52 +110,37 @@ class BERT(nn.Module):
         return load_bert(path, _native_lib=_native_lib)
 
     # ---- native model ----------------------------------------------------------------------------------------------------------
-    def _lib(self):
-        return self._native_lib if self._native_lib is not None else nat.load_native()
+    def _native_version(self):
+        return self.text_model.version()
 
-    def _model(self):
+    def _build_native(self, keep):
         """The prepared weight tables (q | k | v stacked, 1/8 folded into the q rows -- a power of two: no bit changes) and the C
-        structs over them; rebuilt when a parameter was replaced, written or moved since."""
-        ver = self.text_model.version()
-        if self._prepared is None or self._prepared[0] != ver:
-            sd = {k: v.detach().float() for k, v in self.text_model.state_dict().items()}
-            keep, c = [], self.cfg
+        structs over them."""
+        sd = {k: v.detach().float() for k, v in self.text_model.state_dict().items()}
+        c = self.cfg
 
-            def own(t):          # own storage: 16-byte aligned, unaffected by later loads
-                t = t.contiguous().clone()
-                keep.append(t)
-                return t.data_ptr()
+        def own(t):          # own storage: 16-byte aligned, unaffected by later loads
+            t = t.contiguous().clone()
+            keep.append(t)
+            return t.data_ptr()
 
-            layers = (nat.MdmTextLayer * c["n_layers"])()
-            for n in range(c["n_layers"]):
-                p = f"transformer.layer.{n}."
-                qkv_w = torch.cat([sd[p + "attention.q_lin.weight"] * 0.125, sd[p + "attention.k_lin.weight"], sd[p + "attention.v_lin.weight"]], 0)
-                qkv_b = torch.cat([sd[p + "attention.q_lin.bias"] * 0.125, sd[p + "attention.k_lin.bias"], sd[p + "attention.v_lin.bias"]], 0)
-                layers[n] = nat.MdmTextLayer(
-                    qkv_w=own(qkv_w), qkv_b=own(qkv_b), out_w=own(sd[p + "attention.out_lin.weight"]), out_b=own(sd[p + "attention.out_lin.bias"]),
-                    sa_ln_g=own(sd[p + "sa_layer_norm.weight"]), sa_ln_b=own(sd[p + "sa_layer_norm.bias"]),
-                    lin1_w=own(sd[p + "ffn.lin1.weight"]), lin1_b=own(sd[p + "ffn.lin1.bias"]),
-                    lin2_w=own(sd[p + "ffn.lin2.weight"]), lin2_b=own(sd[p + "ffn.lin2.bias"]),
-                    out_ln_g=own(sd[p + "output_layer_norm.weight"]), out_ln_b=own(sd[p + "output_layer_norm.bias"]))
-            model = nat.MdmTextModel(
-                word_emb=own(sd["embeddings.word_embeddings.weight"]), pos_emb=own(sd["embeddings.position_embeddings.weight"]),
-                emb_ln_g=own(sd["embeddings.LayerNorm.weight"]), emb_ln_b=own(sd["embeddings.LayerNorm.bias"]), layers=layers,
-                n_layers=c["n_layers"], dim=c["dim"], n_heads=c["n_heads"], hidden=c["hidden"], vocab=c["vocab"], max_pos=c["max_pos"],
-                ln_eps=LN_EPS)
-            self._prepared = (ver, model, (keep, layers))
-            self._ws = {}
-        return self._prepared[1]
-
-    def _workspace(self, lib, model, B, L, dev, stream):
-        key = (B, L, str(dev), stream)       # (per stream: two streams may be inside the encoder at once)
-        if key not in self._ws:
-            nbytes = lib.mdm_text_workspace_bytes(nat.C.byref(model), B, L)
-            if nbytes == 0:
-                lib.check(-1, "mdm_text_workspace_bytes")
-            if len(self._ws) >= 8:           # (prompt batches come in few shapes; an odd caller must not pile workspaces up)
-                self._ws = {}
-            self._ws[key] = (torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes)
-        return self._ws[key]
+        layers = (nat.MdmTextLayer * c["n_layers"])()
+        for n in range(c["n_layers"]):
+            p = f"transformer.layer.{n}."
+            qkv_w = torch.cat([sd[p + "attention.q_lin.weight"] * 0.125, sd[p + "attention.k_lin.weight"], sd[p + "attention.v_lin.weight"]], 0)
+            qkv_b = torch.cat([sd[p + "attention.q_lin.bias"] * 0.125, sd[p + "attention.k_lin.bias"], sd[p + "attention.v_lin.bias"]], 0)
+            layers[n] = nat.MdmTextLayer(
+                qkv_w=own(qkv_w), qkv_b=own(qkv_b), out_w=own(sd[p + "attention.out_lin.weight"]), out_b=own(sd[p + "attention.out_lin.bias"]),
+                sa_ln_g=own(sd[p + "sa_layer_norm.weight"]), sa_ln_b=own(sd[p + "sa_layer_norm.bias"]),
+                lin1_w=own(sd[p + "ffn.lin1.weight"]), lin1_b=own(sd[p + "ffn.lin1.bias"]),
+                lin2_w=own(sd[p + "ffn.lin2.weight"]), lin2_b=own(sd[p + "ffn.lin2.bias"]),
+                out_ln_g=own(sd[p + "output_layer_norm.weight"]), out_ln_b=own(sd[p + "output_layer_norm.bias"]))
+        keep.append(layers)
+        return nat.MdmTextModel(
+            word_emb=own(sd["embeddings.word_embeddings.weight"]), pos_emb=own(sd["embeddings.position_embeddings.weight"]),
+            emb_ln_g=own(sd["embeddings.LayerNorm.weight"]), emb_ln_b=own(sd["embeddings.LayerNorm.bias"]), layers=layers,
+            n_layers=c["n_layers"], dim=c["dim"], n_heads=c["n_heads"], hidden=c["hidden"], vocab=c["vocab"], max_pos=c["max_pos"],
+            ln_eps=LN_EPS)
 
     # ---- the encoder -----------------------------------------------------------------------------------------------------------
     def check_ids(self, input_ids, attention_mask):
@@ -187,15 +171,12 @@ class BERT(nn.Module):
         B, L = ids.shape
         lib, model = self._lib(), self._model()
         dev = self.text_model.device
-        emulation = not lib.path.endswith(nat.LIB_NAME)
-        if not emulation and dev.type != "cuda":
-            raise nat.MdmError("the MI355X HIP path needs the text encoder's parameters on a cuda (ROCm) device; got " + str(dev))
-        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+        stream = self._stream(lib, dev, "the text encoder's parameters")
         ids_dev = ids.to(torch.int32).contiguous().to(dev)
         lens_dev = lens.to(torch.int32).contiguous().to(dev)
         D = self.cfg["dim"]
         out = torch.empty((L, B, D) if token_major else (B, L, D), dtype=torch.float32, device=dev)
-        ws, nbytes = self._workspace(lib, model, B, L, dev, stream)
+        ws, nbytes = self._workspace("mdm_text_workspace_bytes", model, B, L, dev=dev, stream=stream, cache=True)
         lib.check(lib.mdm_text_encode(nat.C.byref(model), ids_dev.data_ptr(), lens_dev.data_ptr(), out.data_ptr(), B, L, int(bool(token_major)),
                                       ws.data_ptr(), nbytes, stream), "mdm_text_encode")
         return out
