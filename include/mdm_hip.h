@@ -173,8 +173,11 @@ int mdm_set_time_add(mdm_model_t* m, const float* add_dev, int32_t B);
  * ([max_len, latent_dim], computed by the host exactly as model/mdm.py:301-305 does). */
 int mdm_set_weight(mdm_model_t* m, const char* name, const float* dev_ptr, int64_t numel);
 
-/* Bytes of caller-owned, model-lifetime device scratch for derived tables (16-byte-aligned padded
- * poseEmbedding weight, the time-MLP table TimestepEmbedder(pe[t]) for every t: model/mdm.py:316-330). */
+/* Bytes of the caller-owned, model-lifetime device block that holds everything mdm_prepare derives from the weights: the padded
+ * poseEmbedding weight and the time-MLP table TimestepEmbedder(pe[t]) for every t (model/mdm.py:316-330), the fragment-ordered 16-bit
+ * hi | lo planes of every layer weight, the weights with their LayerNorm folded in (planes, column sums, biases; trans_dec: fp32 copies
+ * too) and, for trans_dec, the stacked cross-attention K | V projections of all layers.  Exactly what mdm_prepare writes: one layout
+ * (csrc/model_setup.h carve_const) gives this size and carves the block.  Depends on the mdm_config_t only. */
 size_t mdm_const_bytes(const mdm_model_t* m);
 /* Validates that every weight is present and (re)builds the derived tables.  Call again after weights change. */
 int mdm_prepare(mdm_model_t* m, void* const_ws_dev, size_t const_ws_bytes, void* stream);

@@ -133,56 +133,68 @@ struct AuxStreams {
 #endif
 };
 
-struct mdm_model {
+// What mdm_prepare derives from the weights, all of it inside ONE caller-owned block, the constant workspace.  carve_const
+// (model_setup.h) is the one statement of that block's layout: it returns this struct -- pointers into the block, or null pointers
+// when it is only asked for `bytes` -- and the handle keeps it as its base, so m->planes, m->time_table ... are the carved regions.
+struct ConstBlock {
+  // ---- constants of both architectures
+  int* range_flag = nullptr;    // device word 0 of the block: a weight left the 16-bit planes' range (mdm_prepare)
+  float* w_in_pad = nullptr;    // [D][JFpad]
+  float* time_table = nullptr;  // [max_len][D]
+  float* hidden = nullptr;      // [max_len][D]: the time MLP's first layer, scratch of mdm_prepare
+  X3Weights out_planes_f{nullptr, nullptr};   // poseFinal.weight with the last LayerNorm folded in ...
+  float *c_out = nullptr, *b_out = nullptr;   // ... its column sums and folded bias
+  // ---- trans_enc
+  struct LayerPlanes { X3Weights in_proj, out_proj, linear1, linear2; };
+  std::vector<LayerPlanes> planes;  // fragment-ordered hi/lo planes of the encoder weights (mdm_prepare)
+  X3Weights out_planes{nullptr, nullptr};  // poseFinal.weight, rows padded to jf_out (f16x3 OutputProcess)
+  float* out_bias_pad = nullptr;            // poseFinal.bias padded to jf_out
+  float* scratch_w = nullptr;               // one fp32 matrix [max(3D, FF)][D]: a gamma-scaled weight between its fold and its pack
+  // LayerNorm folded into its consumers (gemm_x3.h X3Epilogue): gamma-scaled weight planes, column sums, folded biases
+  struct LayerFold { X3Weights in_proj, linear1; float *c_qkv, *b_qkv, *c_1, *b_1; };
+  std::vector<LayerFold> fold;
+  X3Weights in_planes{nullptr, nullptr};   // poseEmbedding.weight, K zero-padded to jf_k (f16x3 InputProcess)
+  // ---- trans_dec
+  // the same fold on fp32 weights (gemm_f32.h LnFold): in_proj(l >= 1) <- norm3(l-1), cross-attention q <- norm1(l),
+  // linear1 <- norm2(l); w = W . diag(gamma), c = row sums of w, b = bias + W . beta
+  struct DecFold { float *w_in, *c_in, *b_in, *w_q, *c_q, *b_q, *w_1, *c_1, *b_1; };
+  std::vector<DecFold> dec_fold;
+  // fragment-ordered fp16 hi/lo planes of the layer weights for the small X3 GEMM (gemm_f32.h X3FragB); in_proj,
+  // q and linear1 from the gamma-folded copies where a LayerNorm is folded (in_proj of layer 0: the plain weight)
+  struct DecPlanes { X3Weights in_proj, out_proj, q, out_proj2, linear1, linear2; };
+  std::vector<DecPlanes> dec_planes;
+  float* wf_out = nullptr;                  // poseFinal.weight . diag(gamma of the last norm3) in fp32, the source of out_planes_f
+  // the key | value rows of every layer's cross-attention in_proj stacked into ONE matrix [L * 2D][D] (+ bias [L * 2D]), so
+  // that a window loop projects its text memory / its steps' time rows for all layers in one launch each (round 6: 16 launches -> 2)
+  float *wkv_all = nullptr, *bkv_all = nullptr;
+  size_t bytes = 0;   // of the whole block (mdm_const_bytes)
+};
+
+struct mdm_model : ConstBlock {
   mdm_config_t cfg;
   Profiler prof;
   AuxStreams aux;
   std::map<std::string, const float*> w;
   std::map<std::string, int64_t> expect;  // name -> numel
   bool prepared = false;
-  int* range_flag = nullptr;    // device word in the const workspace: a weight left the 16-bit planes' range (mdm_prepare)
-  float* w_in_pad = nullptr;    // [D][JFpad]
-  float* time_table = nullptr;  // [max_len][D]
+  int jf = 0, jf_pad = 0, jf_out = 0, jf_k = 0;   // njoints*nfeats; rounded up to a multiple of 4 (jf_pad, jf_out); of 32 (jf_k)
+  bool lnfold = false;                      // f16x3 mode without LayerNorm kernels (set by mdm_prepare)
   // mdm_set_time_add (ABI 10): `time_add_next` is the one-shot binding ([time_add_B][D], caller-owned), `time_add` what the call
   // in flight adds to the timestep embedding of its samples (TimeAddScope; null outside a call and for calls without a binding)
   const float* time_add_next = nullptr;
   int time_add_B = 0;
   const float* time_add = nullptr;
-  bool dec_time_token = false;   // MDM_OPT_DEC_TIME_TOKEN: row 0 of a trans_dec sequence is the timestep embedding (emb_trans_dec)
-  int jf = 0, jf_pad = 0;
+  // ---- options (mdm_set_precision; mdm_set_option / mdm_get_option through model_setup.h's table: one int32_t each)
   int precision = MDM_PREC_F16X3;
-  struct LayerPlanes { X3Weights in_proj, out_proj, linear1, linear2; };
-  std::vector<LayerPlanes> planes;  // fragment-ordered hi/lo planes of the encoder weights (mdm_prepare)
-  // LayerNorm folded into its consumers (gemm_x3.h X3Epilogue): gamma-scaled weight planes, column sums, folded biases
-  struct LayerFold { X3Weights in_proj, linear1; float *c_qkv, *b_qkv, *c_1, *b_1; };
-  std::vector<LayerFold> fold;
-  // trans_dec: the same fold on fp32 weights (gemm_f32.h LnFold): in_proj(l >= 1) <- norm3(l-1), cross-attention q <- norm1(l),
-  // linear1 <- norm2(l); w = W . diag(gamma), c = row sums of w, b = bias + W . beta
-  struct DecFold { float *w_in, *c_in, *b_in, *w_q, *c_q, *b_q, *w_1, *c_1, *b_1; };
-  std::vector<DecFold> dec_fold;
-  // trans_dec: fragment-ordered fp16 hi/lo planes of the layer weights for the small X3 GEMM (gemm_f32.h X3FragB); in_proj,
-  // q and linear1 from the gamma-folded copies where a LayerNorm is folded (in_proj of layer 0: the plain weight)
-  struct DecPlanes { X3Weights in_proj, out_proj, q, out_proj2, linear1, linear2; };
-  std::vector<DecPlanes> dec_planes;
-  X3Weights in_planes{nullptr, nullptr};   // poseEmbedding.weight, K zero-padded to jf_k (f16x3 InputProcess)
-  int jf_k = 0;                             // njoints*nfeats rounded up to a multiple of 32
-  X3Weights out_planes_f{nullptr, nullptr};
-  float *c_out = nullptr, *b_out = nullptr;
-  // trans_dec: the key | value rows of every layer's cross-attention in_proj stacked into ONE matrix [L * 2D][D] (+ bias [L * 2D]), so
-  // that a window loop projects its text memory / its steps' time rows for all layers in one launch each (round 6: 16 launches -> 2)
-  float *wkv_all = nullptr, *bkv_all = nullptr;
-  bool lnfold = false;                      // f16x3 mode without LayerNorm kernels (set by mdm_prepare)
-  X3sOptions x3s;                           // which forwards run on gemm_x3s.h's small tiles (mdm_set_option)
-  int fused_xattn = 3;                      // trans_dec plane route, the cross-attention block: 2 = q projection + memory attention per
+  X3sOptions x3s;                           // which forwards run on gemm_x3s.h's small tiles
+  int32_t fused_xattn = 3;                  // trans_dec plane route, the cross-attention block: 2 = q projection + memory attention per
                                             // (sequence, head) (selfattn_block.h CROSS) + out_proj GEMM; 1 = one kernel (xattn_block.h);
                                             // 0 = q projection, exact-fp32 attention kernel, out_proj: three launches; 3 = by size
-  bool fused_selfattn = true;               // ... and in_proj + self-attention of a (sequence, head) as one kernel (selfattn_block.h)
-  bool enc_shared_l0 = true;                // MDM_OPT_ENC_SHARED_LAYER0: guided forwards compute layer 0's in_proj once per sample (gemm_x3.h PAIR)
-  bool attn_direct = false;                 // attention_x3.h DIRECT: planes from the accumulators, next item's tiles 1, 2 in front of the stores
-  bool attn_wide = true;                    // attention_x3.h WIDE: one 8-wave workgroup per (sequence, head) with copy waves, from 129 tokens on
-  X3Weights out_planes{nullptr, nullptr};  // poseFinal.weight, rows padded to jf_out (f16x3 OutputProcess)
-  float* out_bias_pad = nullptr;            // poseFinal.bias padded to jf_out
-  int jf_out = 0;                           // njoints*nfeats rounded up to a multiple of 4
+  int32_t fused_selfattn = 1;               // ... and in_proj + self-attention of a (sequence, head) as one kernel (selfattn_block.h)
+  int32_t attn_direct = 0;                  // attention_x3.h DIRECT: planes from the accumulators, next item's tiles 1, 2 in front of the stores
+  int32_t dec_time_token = 0;               // MDM_OPT_DEC_TIME_TOKEN: row 0 of a trans_dec sequence is the timestep embedding (emb_trans_dec)
+  int32_t enc_shared_l0 = 1;                // MDM_OPT_ENC_SHARED_LAYER0: guided forwards compute layer 0's in_proj once per sample (gemm_x3.h PAIR)
+  int32_t attn_wide = 1;                    // attention_x3.h WIDE: one 8-wave workgroup per (sequence, head) with copy waves, from 129 tokens on
 
   const float* W(const std::string& k) const { return w.at(k); }
   const float* L(int layer, const char* suffix) const {
