@@ -703,6 +703,55 @@ size_t mdm_clip_text_workspace_bytes(const mdm_clip_text_model_t* model, int32_t
 int mdm_clip_text_encode(const mdm_clip_text_model_t* model, const int32_t* ids_dev, const int32_t* lens_dev, float* out_dev,
                          int32_t B, int32_t L, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- The metrics of the unconstrained evaluation (eval/unconstrained/evaluate.py) on feature matrices [rows, D], fp32, row-major,
+ * on the device: improved precision / recall, KID, the FID statistics, diversity.  (Additive to ABI 10.)
+ *
+ * Common to the five calls: every pointer is a device pointer; feature matrices and fp32 / int32 arrays 4-byte aligned (rows take
+ * 16-byte loads when D % 4 == 0 and the matrix lies on a 16-byte boundary), fp64 outputs 8-byte aligned; D >= 1; rows * D < 2^31.
+ * Refused with a message (mdm_last_error) before anything is launched: a null or misaligned pointer, a size out of range, a
+ * workspace below mdm_metrics_workspace_bytes.  Index tables are trusted to be in range.  Distances are sum_j (a_j - b_j)^2 in fp32,
+ * one fixed order over j for every pair (never the Gram form): d2 of two rows is the same bits in every call, at every position, and
+ * exactly 0 for equal rows.  No atomics; every sum in one fixed order: repeated calls return the same bits.  Each call joins the
+ * one-chain-per-device guard (CONCURRENCY).  No device allocation, no synchronisation, every kernel on `stream`: capture-safe. */
+#define MDM_METRICS_KNN_RADIUS 0
+#define MDM_METRICS_MANIFOLD_MEMBERS 1
+#define MDM_METRICS_GATHER_DIST 2
+#define MDM_METRICS_POLY_MMD 3
+#define MDM_METRICS_FEATURE_STATS 4
+
+/* Bytes of workspace of the call `kind` (MDM_METRICS_*) on `rows` rows; 0 on a bad argument (mdm_last_error says which).
+ * MDM_METRICS_POLY_MMD: rows = the subset size m, subsets = S; 2 S ceil(m / 64) 16 doubles plus 64 bytes; subsets * rows < 2^31 and
+ * subsets < 65536 (chunk the subsets: a subset's result does not depend on the others).  Every other kind: 64 bytes, `subsets` ignored. */
+size_t mdm_metrics_workspace_bytes(int32_t kind, int32_t rows, int32_t subsets);
+
+/* radius2_dev[i] = the (k+1)-th smallest squared distance from row i of a_dev [N, D] to the rows of a_dev, row i itself included
+ * (np.partition(distances, k)[k] of precision_recall.py, squared).  1 <= k <= 7, N >= k + 1.  One launch. */
+int mdm_knn_radius(const float* a_dev, int32_t N, int32_t D, int32_t k, float* radius2_dev, void* workspace_dev, size_t workspace_bytes,
+                   void* stream);
+
+/* member_dev[b] (uint8) = 1 if a row a' of a_dev [NA, D] has d2(b_dev[b], a') <= radius2_dev[a'], else 0, for the NB rows of b_dev;
+ * count_dev (int32) = their sum.  The comparison is in the squared domain, on the values mdm_knn_radius compares.  Two launches. */
+int mdm_manifold_members(const float* a_dev, const float* radius2_dev, int32_t NA, const float* b_dev, int32_t NB, int32_t D,
+                         uint8_t* member_dev, int32_t* count_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* dist_dev[p] = || x[first_dev[p]] - x[second_dev[p]] || for P >= 1 index pairs into x_dev [N, D]; mean_dev (fp64) = their mean,
+ * added in fp64 in a fixed order.  Two launches. */
+int mdm_gather_dist(const float* x_dev, int32_t N, int32_t D, const int32_t* first_dev, const int32_t* second_dev, int32_t P,
+                    float* dist_dev, double* mean_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* kid.py polynomial_mmd with the `unbiased` estimator for S subsets at once: subset s is X = g_dev[idx_g_dev[s]] and
+ * Y = r_dev[idx_r_dev[s]] (index tables [S, m] int32), K = (gamma <x, y> + coef0)^degree with <x, y> in exact fp32 (k ascending) and
+ * everything behind it in fp64; mmd2_dev[s] and var_dev[s] (fp64; var at `var_at_m` >= 2) from _mmd2_and_variance's sums.
+ * m >= 3, degree >= 1.  No m x m matrix is written.  Two launches. */
+int mdm_poly_mmd(const float* g_dev, int32_t Ng, const float* r_dev, int32_t Nr, int32_t D, const int32_t* idx_g_dev,
+                 const int32_t* idx_r_dev, int32_t S, int32_t m, double gamma, double coef0, int32_t degree, int32_t var_at_m,
+                 double* mmd2_dev, double* var_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* mu_dev [D] = the column means, sigma_dev [D, D] = the covariance (two-pass, centred, divisor N - 1: np.cov(rowvar=False)) of
+ * x_dev [N, D], both in fp64.  N >= 2, D * D < 2^31.  Two launches. */
+int mdm_feature_stats(const float* x_dev, int32_t N, int32_t D, double* mu_dev, double* sigma_dev, void* workspace_dev,
+                      size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

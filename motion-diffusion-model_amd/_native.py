@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = [
     "mdm_stgcn_workspace_bytes", "mdm_stgcn_forward",
     "mdm_gru_cls_workspace_bytes", "mdm_gru_cls_forward",
     "mdm_clip_text_workspace_bytes", "mdm_clip_text_encode",
+    "mdm_metrics_workspace_bytes", "mdm_knn_radius", "mdm_manifold_members", "mdm_gather_dist", "mdm_poly_mmd", "mdm_feature_stats",
 ]
 # include/mdm_hip_probe.h: exported by the probe build only
 PROBE_SYMBOLS = ["mdm_debug_set", "mdm_debug_get", "mdm_linear_f16f6", "mdm_linear_f16f6_scratch_bytes", "mdm_probe_in_proj",
@@ -123,6 +124,8 @@ class MdmClipTextModel(C.Structure):
                [(n, C.c_int32) for n in ("n_layers", "dim", "n_heads", "mlp", "vocab", "max_pos", "embed")]
 
 
+METRICS_KINDS = {"knn_radius": 0, "manifold_members": 1, "gather_dist": 2, "poly_mmd": 3, "feature_stats": 4}      # MDM_METRICS_*
+METRICS_TILE = 64           # csrc/metrics.h MET_TILE
 STGCN_RES = {"none": 0, "identity": 1, "conv": 2}      # MDM_STGCN_RES_*
 STGCN_MAX_BLOCKS, STGCN_MAX_NEIGHBOURS = 16, 8
 
@@ -217,6 +220,12 @@ class MdmLib:
             "mdm_stgcn_forward": (C.c_int, [P(MdmStgcnModel), vp, vp, vp, i32, i32, vp, sz, vp]),
             "mdm_gru_cls_workspace_bytes": (sz, [P(MdmGruClsModel), i32, i32]),
             "mdm_gru_cls_forward": (C.c_int, [P(MdmGruClsModel), vp, vp, vp, vp, vp, i32, i32, vp, sz, vp]),
+            "mdm_metrics_workspace_bytes": (sz, [i32, i32, i32]),
+            "mdm_knn_radius": (C.c_int, [vp, i32, i32, i32, vp, vp, sz, vp]),
+            "mdm_manifold_members": (C.c_int, [vp, vp, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
+            "mdm_gather_dist": (C.c_int, [vp, i32, i32, vp, vp, i32, vp, vp, vp, sz, vp]),
+            "mdm_poly_mmd": (C.c_int, [vp, i32, vp, i32, i32, vp, vp, i32, i32, C.c_double, C.c_double, i32, i32, vp, vp, vp, sz, vp]),
+            "mdm_feature_stats": (C.c_int, [vp, i32, i32, vp, vp, vp, sz, vp]),
         }
         probe_sig = {
             "mdm_debug_set": (C.c_int, [C.c_int, C.c_int]),

@@ -39,6 +39,7 @@
 #include "clip_text.h"
 #include "stgcn.h"
 #include "gru_recogniser.h"
+#include "metrics.h"
 
 using namespace mdm;
 
@@ -301,7 +302,8 @@ int mdm_attention_x3(const float* qkv, float* out, const int32_t* lengths, int32
 }  // extern "C"
 
 // The entry points that are not MDM's own, one file per model (each with its helpers in an anonymous namespace): the probe
-// library's, then SMPL, the HumanML3D evaluator, the two text encoders, ST-GCN and the GRU recogniser.
+// library's, then SMPL, the HumanML3D evaluator, the two text encoders, ST-GCN, the GRU recogniser and the
+// metrics of the unconstrained evaluation.
 #ifdef MDM_PROBES
 #include "probe_api.h"
 #endif
@@ -310,3 +312,4 @@ int mdm_attention_x3(const float* qkv, float* out, const int32_t* lengths, int32
 #include "text_api.h"
 #include "stgcn_api.h"
 #include "gru_recogniser_api.h"
+#include "metrics_api.h"

@@ -4,8 +4,9 @@ reads batch["x"]), eval mode, one person per sample.
 
 The modules carry the reference's parameter and buffer names, so `load_state_dict(torch.load('uestc_rot6d_stgcn.tar'))` works as it
 does upstream; the arithmetic is csrc/stgcn.h behind include/mdm_hip.h's mdm_stgcn_forward (exact fp32; no Conv2d / BatchNorm / einsum
-call, and no fall-back when the library is missing).  FID, KID, diversity, multimodality, precision / recall and accuracy
-(eval/a2m/stgcn/*.py, eval/unconstrained/metrics/*.py) run on the returned `features` / `yhat` as they are."""
+call, and no fall-back when the library is missing).  The metrics of the unconstrained evaluation (FID statistics, KID, diversity,
+precision / recall: eval/unconstrained/metrics/*.py) have their device path in mdm_amd/metrics.py; multimodality and accuracy of the
+a2m family (eval/a2m/stgcn/*.py) run on the returned `features` / `yhat` as they are."""
 import pickle
 
 import numpy as np
