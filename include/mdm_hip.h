@@ -752,6 +752,85 @@ int mdm_poly_mmd(const float* g_dev, int32_t Ng, const float* r_dev, int32_t Nr,
 int mdm_feature_stats(const float* x_dev, int32_t N, int32_t D, double* mu_dev, double* sigma_dev, void* workspace_dev,
                       size_t workspace_bytes, void* stream);
 
+/* ---- SMPLify: fitting SMPL to 22 generated joints per frame (visualize/simplify_loc2rot.py joints2smpl over
+ * visualize/joints2smpl/src/smplify.py SMPLify3D, use_lbfgs=True, use_collision=False, joints_category="AMASS", seq_ind = 0).
+ * (Additive to ABI 10.)
+ *
+ * The losses read the 24 skeleton joints only, and those depend on the 24 rotations and on rest joints that are affine in the betas:
+ * no vertex is computed.  One kernel launch per closure evaluation returns the loss, its analytic gradient in the optimiser's flat
+ * layout and, from a fixed-order reduction (no atomics), the loss, max|g| and g . d; the host runs the control flow of
+ * PyTorch 2.10's optim.LBFGS.step with line_search_fn='strong_wolfe' on those scalars and reads them from pinned memory after
+ * every evaluation and every new direction.  mdm_smplify_value_grad and mdm_smplify_fit therefore SYNCHRONISE with `stream`, cannot be
+ * captured into a hipGraph (refused with MDM_EUNSUPPORTED on a capturing stream) and hold the one-chain-per-device guard
+ * (CONCURRENCY) for the whole call.  Every host loop is counted: a call ends whatever the data is.
+ *
+ * Flat layout of the variables, T frames: step 1 (camera_fitting_loss_3d) [global_orient T x 3 | camera_t T x 3]; step 2
+ * (body_fitting_loss_3d) [body_pose T x 69 | betas T x 10 | global_orient T x 3 | camera_t T x 3] -- the order of the reference's
+ * parameter lists.  Frames are [T][22][3] joints, conf [22]. */
+typedef struct {
+  const float* j0;                  /* [24][3]      J_regressor . v_template                                  (device, 16-byte aligned) */
+  const float* jdirs;               /* [24][3][10]  J_regressor . shapedirs                                                             */
+  const float* means;               /* [8][69]      the mixture prior's means (prior.py MaxMixturePrior)                                */
+  const float* precisions;          /* [8][69][69]  its precisions: the float32 inverses of the float32 covariances                     */
+  const float* neg_log_nll_weights; /* [8]          -log(nll_weights)                                                                   */
+  const int32_t* parents;           /* [24]         host; parents[0] = -1, parents[i] < i                                               */
+} mdm_smplify_model_t;
+
+typedef struct {
+  int32_t num_iters;        /* 150: max_iter of both optimisers (max_eval = num_iters * 5 / 4)                    */
+  int32_t history;          /* 100: history_size, at most 128                                                     */
+  int32_t stage1_calls;     /* 10:  step() calls of the camera optimiser                                          */
+  int32_t stage2_calls;     /* num_iters: step() calls of the body optimiser                                      */
+  double step_size;         /* 1e-2: lr                                                                           */
+  double tolerance_grad;    /* 1e-7                                                                               */
+  double tolerance_change;  /* 1e-9                                                                               */
+  double joint_weight;      /* 600   (all weights enter squared, as in customloss.py)                             */
+  double sigma;             /* 100   gmof                                                                         */
+  double pose_prior_weight; /* 4.78 * 1.5                                                                         */
+  double angle_prior_weight;/* 15.2                                                                               */
+  double shape_prior_weight;/* 5                                                                                  */
+  double pose_preserve_weight; /* 5                                                                               */
+  double depth_weight;      /* 100   camera_fitting_loss_3d; its term counts four times (the reference's broadcast) */
+} mdm_smplify_call_t;
+
+/* Bytes of workspace of both calls below at T frames (1 <= T <= 4096): the vectors, five gradient buffers and 2 * history pairs of
+ * 85 T floats each; 0 on a bad argument (mdm_last_error says which). */
+size_t mdm_smplify_workspace_bytes(const mdm_smplify_model_t* model, const mdm_smplify_call_t* call, int32_t T);
+
+/* The loss of step `stage` (1 or 2) and its gradient at the point x_dev (flat layout).  fixed_pose_dev [T][69]: step 1 the body pose,
+ * step 2 preserve_pose; fixed_betas_dev [T][10] and cam_est_dev [T][3] (guess_init_3d): step 1 only.  dir_dev: a direction in the
+ * flat layout, or null.  Writes grad_dev (flat), terms_dev [T][6] (step 2: joints, prior, angle, shape, preserve, total; step 1:
+ * joints, depth -- counted once --, 0, 0, 0, total), joints_dev [T][24][3] (the model joints without the camera; may be null) and on
+ * the host scalars_host[3] = loss, max|g|, g . dir.  A frame's terms and gradient are the same bits at every position and T.  A
+ * non-finite pose, betas, j3d or conf is refused with MDM_EINVAL before any output is written; a loss, gradient or g . dir that is
+ * not finite for another reason (the camera block of x, cam_est, the fixed pose of step 2, dir) is refused with MDM_EINVAL behind
+ * the evaluation: the device outputs are written, scalars_host is not.  Two launches, two reads. */
+int mdm_smplify_value_grad(const mdm_smplify_model_t* model, const mdm_smplify_call_t* call, int32_t stage, const float* x_dev,
+                           const float* dir_dev, const float* fixed_pose_dev, const float* fixed_betas_dev, const float* cam_est_dev,
+                           const float* j3d_dev, const float* conf_dev, int32_t T, float* grad_dev, float* terms_dev, float* joints_dev,
+                           float* scalars_host, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* SMPLify3D.__call__: from init_pose_dev [T][72] (global orient, then body pose) and init_betas_dev [T][10], the camera guess, step 1
+ * and step 2.  Writes pose_out_dev [T][72], betas_out_dev [T][10], cam_out_dev [T][3], joints_out_dev [T][24][3] (the fitted model
+ * joints, without the camera) and thetas_out_dev [25][6][T] (simplify_loc2rot.py:108-112: rot6d of the pose through
+ * axis_angle_to_matrix, row 24 = (j3d[:, 0], 0, 0, 0)), and on the host stats_host[6] = function evaluations, iterations and final
+ * loss of step 1, then of step 2 (its final loss as SMPLify3D reports it, pose_preserve_weight 0).  Once a step() call returns at
+ * its first max|g| <= tolerance_grad check the stage ends: every later call would evaluate the same point and return too.  A
+ * non-finite input is refused with MDM_EINVAL before any output is written. */
+int mdm_smplify_fit(const mdm_smplify_model_t* model, const mdm_smplify_call_t* call, const float* init_pose_dev,
+                    const float* init_betas_dev, const float* j3d_dev, const float* conf_dev, int32_t T, float* pose_out_dev,
+                    float* betas_out_dev, float* cam_out_dev, float* joints_out_dev, float* thetas_out_dev, double* stats_host,
+                    void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The line search of mdm_smplify_fit (PyTorch's _strong_wolfe, c1 = 1e-4, c2 = 0.9) on a recorded objective, host only:
+ * evaluation i returns f_seq[i] and gtd_seq[i] whatever step it asks for, and the step it asked for is written to t_seq[i].  Starts
+ * at step t0 from (f0, gtd0) with max|d| = d_norm.  float32_tensors != 0: g . d and max|d| are 0-dim float32 tensors as in the fit
+ * (every value derived from them is rounded to float, as PyTorch does); 0: everything in double.  Returns the number of evaluations,
+ * the final step and its loss. */
+int mdm_smplify_strong_wolfe(const double* f_seq, const double* gtd_seq, int32_t n_seq, double t0, double f0, double gtd0, double d_norm,
+                             double tolerance_change, int32_t max_ls, int32_t float32_tensors, double* t_seq, int32_t* n_evals,
+                             double* t_final, double* f_final);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "mdm_gru_cls_workspace_bytes", "mdm_gru_cls_forward",
     "mdm_clip_text_workspace_bytes", "mdm_clip_text_encode",
     "mdm_metrics_workspace_bytes", "mdm_knn_radius", "mdm_manifold_members", "mdm_gather_dist", "mdm_poly_mmd", "mdm_feature_stats",
+    "mdm_smplify_workspace_bytes", "mdm_smplify_value_grad", "mdm_smplify_fit", "mdm_smplify_strong_wolfe",
 ]
 # include/mdm_hip_probe.h: exported by the probe build only
 PROBE_SYMBOLS = ["mdm_debug_set", "mdm_debug_get", "mdm_linear_f16f6", "mdm_linear_f16f6_scratch_bytes", "mdm_probe_in_proj",
@@ -124,6 +125,28 @@ class MdmClipTextModel(C.Structure):
                [(n, C.c_int32) for n in ("n_layers", "dim", "n_heads", "mlp", "vocab", "max_pos", "embed")]
 
 
+class MdmSmplifyModel(C.Structure):
+    """include/mdm_hip.h mdm_smplify_model_t: device pointers of the rest-joint tables and the mixture prior (parents: host)."""
+    _fields_ = [(n, C.c_void_p) for n in ("j0", "jdirs", "means", "precisions", "neg_log_nll_weights")] + [("parents", C.POINTER(C.c_int32))]
+
+
+class MdmSmplifyCall(C.Structure):
+    """include/mdm_hip.h mdm_smplify_call_t; the defaults are SMPLify3D's as simplify_loc2rot.py constructs it."""
+    _fields_ = [(n, C.c_int32) for n in ("num_iters", "history", "stage1_calls", "stage2_calls")] + \
+               [(n, C.c_double) for n in ("step_size", "tolerance_grad", "tolerance_change", "joint_weight", "sigma", "pose_prior_weight",
+                                          "angle_prior_weight", "shape_prior_weight", "pose_preserve_weight", "depth_weight")]
+
+    def __init__(self, num_iters=150, history=100, stage1_calls=10, stage2_calls=None, **over):
+        kw = dict(step_size=1e-2, tolerance_grad=1e-7, tolerance_change=1e-9, joint_weight=600.0, sigma=100.0,
+                  pose_prior_weight=4.78 * 1.5, angle_prior_weight=15.2, shape_prior_weight=5.0, pose_preserve_weight=5.0,
+                  depth_weight=100.0)
+        kw.update(over)
+        super().__init__(num_iters=num_iters, history=history, stage1_calls=stage1_calls,
+                         stage2_calls=num_iters if stage2_calls is None else stage2_calls, **kw)
+
+
+SMPLIFY_FRAMES = 32         # csrc/smplify.h SMF_FRAMES: frames per workgroup
+SMPLIFY_TERMS = 6           # SMF_TERMS
 METRICS_KINDS = {"knn_radius": 0, "manifold_members": 1, "gather_dist": 2, "poly_mmd": 3, "feature_stats": 4}      # MDM_METRICS_*
 METRICS_TILE = 64           # csrc/metrics.h MET_TILE
 STGCN_RES = {"none": 0, "identity": 1, "conv": 2}      # MDM_STGCN_RES_*
@@ -226,6 +249,13 @@ class MdmLib:
             "mdm_gather_dist": (C.c_int, [vp, i32, i32, vp, vp, i32, vp, vp, vp, sz, vp]),
             "mdm_poly_mmd": (C.c_int, [vp, i32, vp, i32, i32, vp, vp, i32, i32, C.c_double, C.c_double, i32, i32, vp, vp, vp, sz, vp]),
             "mdm_feature_stats": (C.c_int, [vp, i32, i32, vp, vp, vp, sz, vp]),
+            "mdm_smplify_workspace_bytes": (sz, [P(MdmSmplifyModel), P(MdmSmplifyCall), i32]),
+            "mdm_smplify_value_grad": (C.c_int, [P(MdmSmplifyModel), P(MdmSmplifyCall), i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp,
+                                                 P(f32), vp, sz, vp]),
+            "mdm_smplify_fit": (C.c_int, [P(MdmSmplifyModel), P(MdmSmplifyCall), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, P(C.c_double),
+                                          vp, sz, vp]),
+            "mdm_smplify_strong_wolfe": (C.c_int, [P(C.c_double), P(C.c_double), i32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                   C.c_double, i32, i32, P(C.c_double), P(i32), P(C.c_double), P(C.c_double)]),
         }
         probe_sig = {
             "mdm_debug_set": (C.c_int, [C.c_int, C.c_int]),

@@ -40,6 +40,7 @@
 #include "stgcn.h"
 #include "gru_recogniser.h"
 #include "metrics.h"
+#include "smplify.h"
 
 using namespace mdm;
 
@@ -302,8 +303,8 @@ int mdm_attention_x3(const float* qkv, float* out, const int32_t* lengths, int32
 }  // extern "C"
 
 // The entry points that are not MDM's own, one file per model (each with its helpers in an anonymous namespace): the probe
-// library's, then SMPL, the HumanML3D evaluator, the two text encoders, ST-GCN, the GRU recogniser and the
-// metrics of the unconstrained evaluation.
+// library's, then SMPL, the HumanML3D evaluator, the two text encoders, ST-GCN, the GRU recogniser, the
+// metrics of the unconstrained evaluation and the SMPLify fit.
 #ifdef MDM_PROBES
 #include "probe_api.h"
 #endif
@@ -313,3 +314,4 @@ int mdm_attention_x3(const float* qkv, float* out, const int32_t* lengths, int32
 #include "stgcn_api.h"
 #include "gru_recogniser_api.h"
 #include "metrics_api.h"
+#include "smplify_api.h"
