@@ -226,14 +226,8 @@ int launch_linear_f6_debug(Profiler* pf, const float* in, int ld_in, const float
   const size_t wfrag = align_up(x3_packed_weight_elems(N, K) * 2, 256);
   const size_t need = f6_plane_bytes(M, K) + 2 * wfrag;
   if (need > g_f6_dbg_bytes) {
-#ifdef MDM_EMU
-    free(g_f6_dbg_scratch);
-    g_f6_dbg_scratch = malloc(need);
-#else
-    if (hipDeviceSynchronize() != hipSuccess) return fail(MDM_EHIP, "f16f6 debug mode: synchronize failed");
-    if (g_f6_dbg_scratch != nullptr) (void)hipFree(g_f6_dbg_scratch);
-    if (hipMalloc(&g_f6_dbg_scratch, need) != hipSuccess) { g_f6_dbg_scratch = nullptr; g_f6_dbg_bytes = 0; return fail(MDM_EHIP, "f16f6 debug mode: hipMalloc failed"); }
-#endif
+    g_f6_dbg_bytes = 0;
+    if (int rc = rt_grow(&g_f6_dbg_scratch, need)) return rc;
     g_f6_dbg_bytes = need;
   }
   ProfScope ps(pf, MDM_PROF_LINEAR, 2.0 * M * (double)N * K, s);

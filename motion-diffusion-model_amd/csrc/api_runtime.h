@@ -18,11 +18,21 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
+// This file is the emulator's stand-in for the HIP runtime: what the host code asks of the runtime goes through the rt_* helpers
+// and the structs below, each with both bodies, so that no other host file tests MDM_EMU (common.h holds the device side's, and
+// rt_device_ordinal / rt_dyn_lds_once / rt_cu_count, which the launchers in the kernel headers need).  In the emulator a "device"
+// pointer is a host pointer and every launch has finished when it returns.
 #ifdef MDM_EMU
+#define MDM_BUILD_INFO_EMU "1"
 inline int rt_launch_status() { return 0; }
 inline int rt_copy(void* dst, const void* src, size_t bytes, hipStream_t) { memcpy(dst, src, bytes); return 0; }
 template <class K> inline int rt_allow_lds(K, size_t) { return 0; }
+inline int rt_zero(void* dst, size_t bytes, hipStream_t) { memset(dst, 0, bytes); return 0; }
+inline int rt_read_back(void* dst, const void* src, size_t bytes, hipStream_t) { memcpy(dst, src, bytes); return 0; }
+inline bool rt_is_capturing(hipStream_t) { return false; }
+inline int rt_grow(void** p, size_t bytes) { free(*p); *p = malloc(bytes); return *p != nullptr ? 0 : MDM_EHIP; }
 #else
+#define MDM_BUILD_INFO_EMU "0"
 inline int rt_launch_status() {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(MDM_EHIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
@@ -37,6 +47,33 @@ template <class K> inline int rt_allow_lds(K kernel, size_t bytes) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return fail(MDM_EHIP, std::string("hipFuncSetAttribute failed: ") + hipGetErrorString(e));
+  return 0;
+}
+inline int rt_zero(void* dst, size_t bytes, hipStream_t s) {   // stream-ordered
+  return hipMemsetAsync(dst, 0, bytes, s) == hipSuccess ? 0 : fail(MDM_EHIP, "hipMemsetAsync failed");
+}
+// `bytes` (at most 4096) from the device to `dst` behind everything `s` holds: one copy into pinned memory and one synchronisation.
+// The 4 KB pinned buffer is allocated at a thread's first read and kept until the process ends (never freed: one per calling thread).
+inline int rt_read_back(void* dst, const void* src, size_t bytes, hipStream_t s) {
+  static thread_local void* pinned = nullptr;
+  if (pinned == nullptr && hipHostMalloc(&pinned, 4096, hipHostMallocDefault) != hipSuccess) {
+    pinned = nullptr;
+    return fail(MDM_EHIP, "hipHostMalloc of the 4 KB read-back buffer failed");
+  }
+  if (hipMemcpyAsync(pinned, src, bytes, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return fail(MDM_EHIP, "reading values back from the device failed");
+  memcpy(dst, pinned, bytes);
+  return 0;
+}
+inline bool rt_is_capturing(hipStream_t s) {   // into a hipGraph
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+}
+// A library-owned device block (debug paths only) replaced by one of `bytes` bytes, behind everything the device holds; on failure *p is null.
+inline int rt_grow(void** p, size_t bytes) {
+  if (hipDeviceSynchronize() != hipSuccess) return fail(MDM_EHIP, "hipDeviceSynchronize failed");
+  if (*p != nullptr) (void)hipFree(*p);
+  if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; return fail(MDM_EHIP, "hipMalloc failed"); }
   return 0;
 }
 #endif
@@ -73,8 +110,11 @@ inline int lds_fail(int rc, const char* what) {
 // Opt-in per-launch timing (mdm_profile_enable): one hipEvent pair per kernel launch, bucketed by kernel class.
 struct Profiler {
   bool on = false;
+  // read(): total time, launches and flops of one class so far (waits for its last launch), 0 or an error code; reset(): forget them
 #ifdef MDM_EMU
   int64_t launches[MDM_PROF_NUM] = {};   // the CPU emulation has no events: it counts the scopes per class (times and flops read 0)
+  int read(int cat, double& ms, int64_t& n, double& fl) const { ms = 0.0; fl = 0.0; n = launches[cat]; return 0; }
+  void reset() { for (auto& c : launches) c = 0; }
 #else
   struct Rec { int cat; hipEvent_t a, b; double flops; };
   std::vector<Rec> recs;
@@ -84,6 +124,21 @@ struct Profiler {
     hipEvent_t e = nullptr;
     (void)hipEventCreate(&e);
     return e;
+  }
+  int read(int cat, double& ms, int64_t& n, double& fl) const {
+    ms = 0.0; fl = 0.0; n = 0;
+    for (const auto& r : recs) {
+      if (r.cat != cat) continue;
+      if (hipEventSynchronize(r.b) != hipSuccess) return fail(MDM_EHIP, "mdm_profile_read: hipEventSynchronize failed");
+      float dt = 0.f;
+      if (hipEventElapsedTime(&dt, r.a, r.b) != hipSuccess) return fail(MDM_EHIP, "mdm_profile_read: hipEventElapsedTime failed");
+      ms += dt; fl += r.flops; ++n;
+    }
+    return 0;
+  }
+  void reset() {
+    for (auto& r : recs) { pool.push_back(r.a); pool.push_back(r.b); }
+    recs.clear();
   }
   ~Profiler() {
     for (auto& r : recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -110,9 +165,14 @@ struct ProfScope {   // records start on construction, stop on destruction (both
 
 // Side streams of a model handle (probe build: the DiP window loop's concurrent sample groups, see mdm_sample_loop_dec): created
 // on first use on the handle's device, joined back into the caller's stream with events before the call returns.
+// fork_from(s, G, gs): gs[1 .. G) become side streams that start behind everything `s` holds (gs[0] stays `s`); join_into(s, G, gs):
+// `s` continues behind them.  The emulator has one stream: gs stays as it is, both are no-ops.
 struct AuxStreams {
   static constexpr int kMax = 3;
-#ifndef MDM_EMU
+#ifdef MDM_EMU
+  int fork_from(hipStream_t, int, hipStream_t*) { return MDM_OK; }
+  int join_into(hipStream_t, int, const hipStream_t*) { return MDM_OK; }
+#else
   hipStream_t s[kMax] = {};
   hipEvent_t fork = nullptr, join[kMax] = {};
   int n = 0;
@@ -121,6 +181,22 @@ struct AuxStreams {
     for (; n < want && n < kMax; ++n)
       if (hipStreamCreateWithFlags(&s[n], hipStreamNonBlocking) != hipSuccess ||
           hipEventCreateWithFlags(&join[n], hipEventDisableTiming) != hipSuccess) return fail(MDM_EHIP, "hipStreamCreate failed");
+    return MDM_OK;
+  }
+  int fork_from(hipStream_t main, int G, hipStream_t* gs) {
+    if (G <= 1) return MDM_OK;
+    if (int rc = ensure(G - 1)) return rc;
+    if (hipEventRecord(fork, main) != hipSuccess) return fail(MDM_EHIP, "side streams: hipEventRecord failed");
+    for (int g = 1; g < G; ++g) {
+      gs[g] = s[g - 1];
+      if (hipStreamWaitEvent(gs[g], fork, 0) != hipSuccess) return fail(MDM_EHIP, "side streams: hipStreamWaitEvent failed");
+    }
+    return MDM_OK;
+  }
+  int join_into(hipStream_t main, int G, const hipStream_t* gs) {
+    for (int g = 1; g < G; ++g)
+      if (hipEventRecord(join[g - 1], gs[g]) != hipSuccess || hipStreamWaitEvent(main, join[g - 1], 0) != hipSuccess)
+        return fail(MDM_EHIP, "side streams: joining failed");
     return MDM_OK;
   }
   ~AuxStreams() {

@@ -41,11 +41,7 @@ __global__ __launch_bounds__(256) void attention_x3_long_kernel(QkvPlanes P, con
   MDM_DYN_SMEM(unsigned char, lds);
   const int SP = P.SP, NKT = P.NKT, H = P.H;
   const int tid = threadIdx.x, lane = tid & 63;
-#ifdef MDM_EMU
-  const int w = tid >> 6;
-#else
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-#endif
+  const int w = wave_index(tid);
   const int r = lane & 31, h = lane >> 5;
   const int item = (int)blockIdx.x / nqb, qb = (int)blockIdx.x - item * nqb;
   const int seq = item / H, head = item - seq * H;

@@ -62,28 +62,8 @@ static_assert(AX_SLOT + 4 * 32 * AX_OST * 4 <= AX_RING * AX_SLOT, "output stagin
 // moment the item's last tile has been consumed, and the NEXT item's key tiles 1 and 2 are requested right behind the closing
 // rendezvous, in front of the stores; the item then starts without a queue drain: its first three tile waits count the stores that are
 // still in flight (32 per active wave; vmcnt counts stores on gfx9).  Planes only (the model's path); the fp32-output form of the
-// building-block API keeps the staged epilogue.
-template <int N> __device__ __forceinline__ void ax_vm_wait() {      // s_waitcnt vmcnt(N), N <= 63 (common.h's builtin form stops at 15)
-#ifdef MDM_EMU
-  emu::vm_wait(N);
-#else
-  asm volatile("s_waitcnt vmcnt(%0)" : : "i"(N) : "memory");
-#endif
-}
-// DIRECT's plane stores are COUNTED by the next item's first tile waits (AX_NST = 32 per active wave): they are issued from inline
-// asm, one instruction per plane and register quad, so that the count cannot follow a compiler decision to merge, split or reorder
-// them (the C++ form relied on hipcc emitting exactly two 8-byte stores per call).
-__device__ __forceinline__ void ax_split4_store_counted(p16_t* hi_p, p16_t* lo_p, float4 v) {
-#ifdef MDM_EMU
-  split4_store(hi_p, lo_p, v);
-#else
-  uint32_t h01, l01, h23, l23;
-  split2_p16(v.x, v.y, h01, l01);
-  split2_p16(v.z, v.w, h23, l23);
-  asm volatile("global_store_dwordx2 %0, %1, off" : : "v"(hi_p), "v"(u32x2{h01, h23}) : "memory");
-  asm volatile("global_store_dwordx2 %0, %1, off" : : "v"(lo_p), "v"(u32x2{l01, l23}) : "memory");
-#endif
-}
+// building-block API keeps the staged epilogue.  DIRECT's plane stores are COUNTED by the next item's first tile waits (AX_NST = 32
+// per active wave; common.h split4_store_counted, vmem_wait_bare, kStoresInVmcnt).
 template <int NKT, bool DIRECT>
 __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const int* __restrict__ lengths,
                                                                     int S, int D, int B, int lead, float* __restrict__ out,
@@ -95,11 +75,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-#ifdef MDM_EMU
-  const int w = tid >> 6;
-#else
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-#endif
+  const int w = wave_index(tid);
   const int r = lane & 31, h = lane >> 5;
   const int H = P.H;
   // virtual blocks vb and vb+8 run on the same XCD (block -> XCD b % 8; the grid is a multiple of 16): they are the two query
@@ -175,9 +151,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
     reinterpret_cast<float*>(lds + AX_RING * AX_SLOT)[tid] = ok ? 0.f : -INFINITY;
   }
   int lv = lane;
-#ifndef MDM_EMU
-  asm volatile("" : "+v"(lv));   // opaque per item: nothing derived from it is hoisted out of the item loop
-#endif
+  opaque_v(lv);   // opaque per item: nothing derived from it is hoisted out of the item loop
 
   const bool carried = DIRECT && !first_item;     // tiles 1, 2 are on their way and the previous item's stores may be in flight
   if (!carried) {
@@ -199,9 +173,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
   // V^T row r of a 32-d block, chunk h ^ ((r>>2)&3) (s2 flips chunk bit 1)
   const uint32_t klane = (uint32_t)(r * 256 + ((h ^ (r & 15)) * 16));
   const uint32_t vlane = (uint32_t)(r * 64 + ((h ^ ((r >> 2) & 3)) * 16));
-#ifndef MDM_EMU
-  const uint32_t lbase = lds_addr_of(lds);
-#endif
+  const LdsAddr lbase = lds_addr_of(lds);
 
   static_for<NTILES>([&](auto t_tag) __attribute__((always_inline)) {
     constexpr int t = decltype(t_tag)::value;
@@ -210,16 +182,10 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
     constexpr int ahead = (NTILES - 1 - t) < 2 ? (NTILES - 1 - t) : 2;
     if constexpr (DIRECT && t < 3 && NTILES > 3) {
       // a carried item: behind tile t sit (t == 0: the 16 Q fragment loads,) the tiles requested since and the previous item's
-      // stores -- issued behind tile 2, in front of tile 3
-      // (the emulator's queue holds the untracked operations only -- LDS-DMA pieces; compiler-tracked loads and stores take effect
-      // at once there: kTrk = 0)
-#ifdef MDM_EMU
-      constexpr int kTrk = 0;
-#else
-      constexpr int kTrk = 1;
-#endif
-      if (carried && active) ax_vm_wait<4 * ahead + kTrk * (AX_NST + (t == 0 ? 16 : 0))>();
-      else if (carried) ax_vm_wait<4 * ahead + kTrk * (t == 0 ? 16 : 0)>();
+      // stores -- issued behind tile 2, in front of tile 3 (compiler-tracked loads count like stores: common.h kStoresInVmcnt)
+      constexpr int kTrk = kStoresInVmcnt;
+      if (carried && active) vmem_wait_bare<4 * ahead + kTrk * (AX_NST + (t == 0 ? 16 : 0))>();
+      else if (carried) vmem_wait_bare<4 * ahead + kTrk * (t == 0 ? 16 : 0)>();
       else wait_vmem_upto<4 * ahead>();
     } else wait_vmem_upto<4 * ahead>();
     wg_barrier();  // tile t visible to every wave; every wave is done with tile t-1 (whose slot is refilled now)
@@ -237,12 +203,8 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
       // ---- phase 1, key tile t: St[key][query] += K . Q^T, three products per 16-deep k step
       if (active) {
         p16x8 kh[3], kl[3];
-#ifdef MDM_EMU
-#define AX_RD_K(dst, plane, st) lds_read16(dst, lds, slot * AX_SLOT + (plane) * 8192 + (klane ^ ((st) << 5)))
-#else
-        const uint32_t kb = lbase + klane;
+        const LdsAddr kb = lbase + klane;
 #define AX_RD_K(dst, plane, st) lds_read16<slot * AX_SLOT + (plane) * 8192>(dst, kb ^ (uint32_t)((st) << 5))
-#endif
         static_for<8 + 2>([&](auto u_tag) __attribute__((always_inline)) {
           constexpr int u = decltype(u_tag)::value;
           if constexpr (u < 8) {
@@ -292,11 +254,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
         for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-#ifdef MDM_EMU
-            const float pe = expf(p[kt][e] - mx);  // exp(-inf) = 0 for masked keys; key 0 is always valid
-#else
-            const float pe = __expf(p[kt][e] - mx);  // v_exp_f32 of a non-positive argument (2 instructions, ~2 ulp)
-#endif
+            const float pe = exp_fast(p[kt][e] - mx);  // of a non-positive argument; exp(-inf) = 0 for masked keys; key 0 is always valid
             p[kt][e] = pe;
             sum += pe;
           }
@@ -314,12 +272,8 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
       }
       if (active) {
         p16x8 vh[3], vl[3], ph, pl;
-#ifdef MDM_EMU
-#define AX_RD_V(dst, plane, s2, dt) lds_read16(dst, lds, slot * AX_SLOT + (plane) * 8192 + (dt) * 2048 + (vlane ^ ((s2) << 5)))
-#else
-        const uint32_t vb = lbase + vlane;
+        const LdsAddr vb = lbase + vlane;
 #define AX_RD_V(dst, plane, s2, dt) lds_read16<slot * AX_SLOT + (plane) * 8192 + (dt) * 2048>(dst, vb ^ (uint32_t)((s2) << 5))
-#endif
         static_for<8 + 2>([&](auto u_tag) __attribute__((always_inline)) {
           constexpr int u = decltype(u_tag)::value;
           if constexpr (u < 8) {
@@ -366,7 +320,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(QkvPlanes P, const
         for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
           for (int g = 0; g < 4; ++g)
-            ax_split4_store_counted(oh + obase + 32 * dt + 8 * g, ol + obase + 32 * dt + 8 * g,
+            split4_store_counted(oh + obase + 32 * dt + 8 * g, ol + obase + 32 * dt + 8 * g,
                                     make_float4(o[dt][4 * g + 0] * inv, o[dt][4 * g + 1] * inv, o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv));
       }
     }
@@ -451,11 +405,7 @@ __global__ __launch_bounds__(AXW_THREADS) void attention_x3_kernel_wide(QkvPlane
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-#ifdef MDM_EMU
-  const int w = tid >> 6;
-#else
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-#endif
+  const int w = wave_index(tid);
   const int H = P.H;
   const int step = (int)gridDim.x;
   int item = (int)blockIdx.x;   // the grid has at most `items` workgroups
@@ -492,9 +442,7 @@ __global__ __launch_bounds__(AXW_THREADS) void attention_x3_kernel_wide(QkvPlane
       // `lv` = the lane id, opaque per item: the per-lane source offsets are the same for every item, and hipcc otherwise hoists all of
       // them out of the item loop and spills them (the kernel's register count is the larger of its two roles')
       int lv = lane;
-#ifndef MDM_EMU
-      asm volatile("" : "+v"(lv));
-#endif
+      opaque_v(lv);
       static_for<NTILES>([&](auto t_tag) __attribute__((always_inline)) {
         constexpr int t = decltype(t_tag)::value;
         constexpr int tn = t + AXW_AHEAD;
@@ -502,8 +450,8 @@ __global__ __launch_bounds__(AXW_THREADS) void attention_x3_kernel_wide(QkvPlane
         else if (has_next) issue_tile((size_t)next, tn - NTILES, axw_slot(first_next, tn - NTILES), lv);
         // tile t landed?  LDS-DMA retires in order; behind it sit the tiles requested since (the stream ends with the last item)
         constexpr int tail = (NTILES - 1 - t) < AXW_AHEAD ? (NTILES - 1 - t) : AXW_AHEAD;
-        if (has_next) ax_vm_wait<PPW * AXW_AHEAD>();
-        else ax_vm_wait<PPW * tail>();
+        if (has_next) vmem_wait_bare<PPW * AXW_AHEAD>();
+        else vmem_wait_bare<PPW * tail>();
         wg_barrier();   // tile t visible to the compute waves; they are done with tile t - 1
       });
       if (!has_next) break;
@@ -530,9 +478,7 @@ __global__ __launch_bounds__(AXW_THREADS) void attention_x3_kernel_wide(QkvPlane
   load_q((size_t)item);
   const uint32_t klane = (uint32_t)(r * 256 + ((h ^ (r & 15)) * 16));
   const uint32_t vlane = (uint32_t)(r * 64 + ((h ^ ((r >> 2) & 3)) * 16));
-#ifndef MDM_EMU
-  const uint32_t lbase = lds_addr_of(lds);
-#endif
+  const LdsAddr lbase = lds_addr_of(lds);
   float* const kmask = reinterpret_cast<float*>(lds + AXW_KMASK_OFF);
   float* const so = reinterpret_cast<float*>(lds + AXW_STAGE_OFF) + w * (32 * AX_OST);   // wave-private
 
@@ -555,11 +501,9 @@ __global__ __launch_bounds__(AXW_THREADS) void attention_x3_kernel_wide(QkvPlane
     kmask[tid] = ok ? 0.f : -INFINITY;
   }
 
-#ifndef MDM_EMU
   // the slot term stays a run-time scalar for every NKT (with twelve tiles `first` is provably 0, and hipcc then keeps the fragment
   // addresses of all six slots in registers across the item: 6 VGPRs spilled at NKT = 6)
-  asm volatile("" : "+s"(first));
-#endif
+  opaque_s(first);
 
   f32x16 p[NKT];
 #pragma unroll
@@ -579,12 +523,8 @@ __global__ __launch_bounds__(AXW_THREADS) void attention_x3_kernel_wide(QkvPlane
       // ---- phase 1, key tile t
       {
         p16x8 kh[3], kl[3];
-#ifdef MDM_EMU
-#define AX_RD_K(dst, plane, st) lds_read16(dst, lds, soff + (plane) * 8192 + (klane ^ ((st) << 5)))
-#else
-        const uint32_t kb = lbase + soff + klane;
+        const LdsAddr kb = lbase + soff + klane;
 #define AX_RD_K(dst, plane, st) lds_read16<(plane) * 8192>(dst, kb ^ (uint32_t)((st) << 5))
-#endif
         static_for<8 + 2>([&](auto u_tag) __attribute__((always_inline)) {
           constexpr int u = decltype(u_tag)::value;
           if constexpr (u < 8) {
@@ -627,11 +567,7 @@ __global__ __launch_bounds__(AXW_THREADS) void attention_x3_kernel_wide(QkvPlane
         for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-#ifdef MDM_EMU
-            const float pe = expf(p[kt][e] - mx);
-#else
-            const float pe = __expf(p[kt][e] - mx);
-#endif
+            const float pe = exp_fast(p[kt][e] - mx);
             p[kt][e] = pe;
             sum += pe;
           }
@@ -649,12 +585,8 @@ __global__ __launch_bounds__(AXW_THREADS) void attention_x3_kernel_wide(QkvPlane
       }
       {
         p16x8 vh[3], vl[3], ph, pl;
-#ifdef MDM_EMU
-#define AX_RD_V(dst, plane, s2, dt) lds_read16(dst, lds, soff + (plane) * 8192 + (dt) * 2048 + (vlane ^ ((s2) << 5)))
-#else
-        const uint32_t vb = lbase + soff + vlane;
+        const LdsAddr vb = lbase + soff + vlane;
 #define AX_RD_V(dst, plane, s2, dt) lds_read16<(plane) * 8192 + (dt) * 2048>(dst, vb ^ (uint32_t)((s2) << 5))
-#endif
         static_for<8 + 2>([&](auto u_tag) __attribute__((always_inline)) {
           constexpr int u = decltype(u_tag)::value;
           if constexpr (u < 8) {

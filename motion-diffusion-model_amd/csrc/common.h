@@ -2,6 +2,12 @@
 //
 // The only non-HIP build of these sources is the CPU test emulator (tests/emu, -DMDM_EMU), which
 // exists because the build container has no GPU; it is test infrastructure, never a product path.
+//
+// RULE: this file is the one place where the two builds part on the device side (api_runtime.h is the one on the host side).
+// A kernel header spells every primitive once, the way the device wants it, and never tests MDM_EMU or names emu:: itself: a
+// statement that the emulator compiles differently from the product is a statement the CPU suite does not check
+// (tests/test_emu_source_rule.py).  A primitive here is a function where that leaves the product's instruction streams as they
+// were, and a macro where it does not (profiles/r21a_emu_forks.md lists which and why).
 #pragma once
 #ifdef MDM_EMU
 #include "hip_emu.h"
@@ -37,14 +43,18 @@ inline int rt_device_ordinal() {
 #endif
 }
 
-#ifndef MDM_EMU
 // The one-time opt-in of a kernel instantiation to more than 64 KB of dynamic LDS, per device (`configured` = that instantiation's
 // static bool[kMaxDevices]).  0: set (now or earlier); -1: the HIP call failed; -3: this would be the instantiation's FIRST use and
 // `stream` is being captured into a hipGraph -- a function-attribute call does not belong inside a capture (a warm-up
 // with another token count / window shape leaves an instantiation unconfigured): the caller reports MDM_EUNSUPPORTED and asks for a
 // warm-up call of the same shapes outside the capture (include/mdm_hip.h "hipGraph CAPTURE").  The capture query runs on a first
 // use only: a configured instantiation costs one array read per launch.
+// (The emulator's workgroups get whatever they ask for: always 0.)
 template <class KF> inline int rt_dyn_lds_once(KF kfn, int bytes, bool* configured, hipStream_t stream) {
+#ifdef MDM_EMU
+  (void)kfn; (void)bytes; (void)configured; (void)stream;
+  return 0;
+#else
   bool& done = configured[rt_device_ordinal()];
   if (done) return 0;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -52,7 +62,66 @@ template <class KF> inline int rt_dyn_lds_once(KF kfn, int bytes, bool* configur
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return -1;
   done = true;
   return 0;
+#endif
 }
+
+// Compute units of the current device, cached per device ordinal (a process may drive several GPUs); 256 where the query fails.
+// The emulator says 3: a persistent grid that small makes its kernels walk through their tile roll-over paths.
+inline int rt_cu_count() {
+#ifdef MDM_EMU
+  return 3;
+#else
+  static int cus_of[kMaxDevices] = {};
+  const int dev = rt_device_ordinal();
+  int& cus = cus_of[dev];
+  if (cus == 0) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
+    if (cus <= 0) cus = 256;
+  }
+  return cus;
+#endif
+}
+
+// Timeline probes (PROBE BUILD ONLY): wave 0 of every workgroup of ONE selected launch of a kernel stamps the shader clock at
+// fixed points into that kernel's `__device__` array, NST stamps per workgroup, for the first WGS workgroups.  A kernel opens with
+// MDM_TL_BEGIN(its __device__ flag) and stamps with MDM_TL_STAMP(array, WGS, NST, i); its launcher calls rt_timeline_switch in front
+// of every launch; mdm_debug_set (probe_api.h) sets the TimelineSel, mdm_debug_get reads the array back through rt_timeline_read.
+#ifdef MDM_PROBES
+struct TimelineSel { int target = -1, count = 0; };   // stamp the target-th launch from the moment it was set; < 0: off
+#define MDM_TL_BEGIN(flag) const bool tl_on = (flag) != 0
+#define MDM_TL_STAMP(arr, WGS, NST, i)                                                                                    \
+  do {                                                                                                                     \
+    if (tl_on && tid == 0 && blockIdx.x < (WGS)) (arr)[(NST) * blockIdx.x + (i)] = __builtin_readcyclecounter();           \
+  } while (0)
+// The launch-time switch: the kernel's flag is set for exactly the selected launch (stream-ordered).  0, or -1: the copy failed.
+inline int rt_timeline_switch(TimelineSel& sel, int& flag, hipStream_t stream, bool* selected = nullptr) {
+  if (selected != nullptr) *selected = false;
+  if (sel.target < 0) return 0;
+  static const int on_v[2] = {0, 1};
+  const int on = (sel.count++ == sel.target) ? 1 : 0;
+  if (selected != nullptr) *selected = on != 0;
+#ifdef MDM_EMU
+  (void)stream;
+  flag = on_v[on];
+#else
+  if (hipMemcpyToSymbolAsync(static_cast<const void*>(&flag), &on_v[on], sizeof(int), 0, hipMemcpyHostToDevice, stream) != hipSuccess) return -1;
+#endif
+  return 0;
+}
+// `n` stamps of a kernel's array to the host, behind everything the device holds.  false: a HIP call failed.
+inline bool rt_timeline_read(unsigned long long* dst, const unsigned long long* arr, size_t n) {
+#ifdef MDM_EMU
+  for (size_t i = 0; i < n; ++i) dst[i] = arr[i];
+  return true;
+#else
+  return hipDeviceSynchronize() == hipSuccess &&
+         hipMemcpyFromSymbol(dst, static_cast<const void*>(arr), n * sizeof(unsigned long long), 0, hipMemcpyDeviceToHost) == hipSuccess;
+#endif
+}
+#else
+#define MDM_TL_BEGIN(flag) do { } while (0)
+#define MDM_TL_STAMP(arr, WGS, NST, i) do { } while (0)
 #endif
 
 // MDM_KERNARGS_NOW: pin the scalar loads of the kernel arguments a kernel's FIRST
@@ -71,6 +140,62 @@ template <class T> __device__ __forceinline__ T* rt_sgpr_ptr(T* p) { asm volatil
 #define MDM_KERNARGS_NOW(...) do { } while (0)
 template <class T> __device__ __forceinline__ T* rt_sgpr_ptr(T* p) { return p; }
 #endif
+
+// Index of the calling thread's wave as a wave-uniform (scalar) value.  A macro on the device: as a function it changed the
+// schedule of every xattn_block_kernel instantiation.
+#ifdef MDM_EMU
+__device__ __forceinline__ int wave_index(int tid) { return tid >> 6; }
+#else
+#define wave_index(tid) __builtin_amdgcn_readfirstlane((tid) >> 6)
+#endif
+
+// Values made opaque to the optimiser (an empty asm statement that claims to rewrite them in place, in a vector / scalar
+// register): nothing derived from an opaque copy is hoisted above this point or merged with what was derived from the original.
+// The emulator has no optimiser to restrain.
+template <class T> __device__ __forceinline__ void opaque_v(T& x) {
+#ifndef MDM_EMU
+  asm volatile("" : "+v"(x));
+#else
+  (void)x;
+#endif
+}
+template <class T> __device__ __forceinline__ void opaque_s(T& a) {
+#ifndef MDM_EMU
+  asm volatile("" : "+s"(a));
+#else
+  (void)a;
+#endif
+}
+template <class T, class U> __device__ __forceinline__ void opaque_s(T& a, U& b) {   // ONE statement for both
+#ifndef MDM_EMU
+  asm volatile("" : "+s"(a), "+s"(b));
+#else
+  (void)a; (void)b;
+#endif
+}
+
+// The hardware's approximate transcendentals; the emulator computes the exact ones (the tests' tolerances cover the ulps).
+__device__ __forceinline__ float exp_fast(float x) {      // v_exp_f32 (2 instructions, ~2 ulp)
+#ifdef MDM_EMU
+  return expf(x);
+#else
+  return __expf(x);
+#endif
+}
+__device__ __forceinline__ float rcp_fast(float x) {      // v_rcp_f32 (1 ulp) instead of the ~10-instruction IEEE divide
+#ifdef MDM_EMU
+  return 1.0f / x;
+#else
+  return __builtin_amdgcn_rcpf(x);
+#endif
+}
+__device__ __forceinline__ float rsqrt_fast(float x) {    // v_rsq_f32 (1 ulp)
+#ifdef MDM_EMU
+  return 1.0f / sqrtf(x);
+#else
+  return __builtin_amdgcn_rsqf(x);
+#endif
+}
 
 // v_mfma_f32_32x32x2_f32: exact-fp32 matrix FMA (64 cyc/SIMD, 157 TF chip peak).
 //   lane l supplies A[i = l&31][k = l>>5] and B[k = l>>5][j = l&31];
@@ -142,6 +267,25 @@ __device__ __forceinline__ f32x4 mfma16_p16(p16x8 a, p16x8 b, f32x4 c) {
   return emu::mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c);
 #else
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+#endif
+}
+
+// v_mfma_f32_16x16x4_f32: lane l supplies A[i = l&15][k = l>>4] and B[k = l>>4][j = l&15]; D[reg] is row 4 (l>>4) + reg, column l&15.
+// 32 cycles per SIMD, 40 dependent (gru_recogniser.h: the three gate accumulators of a wave alternate).
+__device__ __forceinline__ f32x4 mfma16_f32(float a, float b, f32x4 c) {
+#ifdef MDM_EMU
+  // (over the emulator's lane shuffle, so that these sources build against hip_emu.h as it stands)
+  const int l = emu::lane_id(), j = l & 15, q = l >> 4;
+  float bk[4];
+  for (int k = 0; k < 4; ++k) bk[k] = emu::shfl_f32(b, j + 16 * k);
+  for (int r = 0; r < 4; ++r) {
+    float acc = c[r];
+    for (int k = 0; k < 4; ++k) acc = fmaf(emu::shfl_f32(a, 4 * q + r + 16 * k), bk[k], acc);      // k ascending
+    c[r] = acc;
+  }
+  return c;
+#else
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 #endif
 }
 
@@ -327,12 +471,28 @@ __device__ __forceinline__ void static_for(F&& f) {
 // the f16x3 main loop), so the hot loops issue their reads through lds_read16 and retire them IN ORDER with a counted
 // lds_wait<N>(regs...) that names the registers becoming valid -- no consumer of those registers can be scheduled
 // above the wait, and any copy the compiler made earlier is dead.
+//
+// LdsAddr: the address such a read takes -- lds_addr_of(pointer into the workgroup's LDS), then `+ uint32_t`, `- uint32_t` and
+// `^ uint32_t`; the read adds a compile-time byte offset IMM < 65536.  On the device it IS the 32-bit LDS byte address (an alias, so
+// the kernels' address arithmetic compiles to what it always did); in the emulator it is (base pointer, byte offset), the
+// operators act on the offset and the read issues base + offset + IMM.  The kernels XOR their swizzle terms (bits 4 .. 7) into the
+// ABSOLUTE address on the device and into the offset from lds_addr_of's pointer in the emulator: the same bytes only because every
+// such pointer -- the dynamic LDS base plus a multiple of the slot / stage / image size -- is aligned beyond the XOR range.  The
+// kernels rely on that: none of them has static LDS, so the dynamic segment starts at LDS address 0, and the slots are multiples of 1 KB.
 #ifdef MDM_EMU
-__device__ __forceinline__ void lds_read16(p16x8& dst, const unsigned char* base, uint32_t byte_off) {
-  emu::lds_issue(&dst, base + byte_off, 16);   // EARLY mode: immediate; LATE mode: withheld until a covering lds_wait
+struct LdsAddr {
+  const unsigned char* base;
+  uint32_t off;
+};
+__device__ __forceinline__ LdsAddr lds_addr_of(const void* p) { return LdsAddr{static_cast<const unsigned char*>(p), 0u}; }
+__device__ __forceinline__ LdsAddr operator+(LdsAddr a, uint32_t b) { return LdsAddr{a.base, a.off + b}; }
+__device__ __forceinline__ LdsAddr operator-(LdsAddr a, uint32_t b) { return LdsAddr{a.base, a.off - b}; }
+__device__ __forceinline__ LdsAddr operator^(LdsAddr a, uint32_t b) { return LdsAddr{a.base, a.off ^ b}; }
+template <int IMM> __device__ __forceinline__ void lds_read16(p16x8& dst, LdsAddr a) {
+  emu::lds_issue(&dst, a.base + a.off + IMM, 16);   // EARLY mode: immediate; LATE mode: withheld until a covering lds_wait
 }
-__device__ __forceinline__ void lds_refill16(p16x8& slot, const unsigned char* base, uint32_t byte_off) {
-  emu::lds_issue(&slot, base + byte_off, 16);
+template <int IMM> __device__ __forceinline__ void lds_refill16(p16x8& slot, LdsAddr a) {
+  emu::lds_issue(&slot, a.base + a.off + IMM, 16);
 }
 template <int N> __device__ __forceinline__ void lds_wait(p16x8&, p16x8&) { emu::lgkm_wait(N); }
 template <int N> __device__ __forceinline__ void lds_wait(p16x8&, p16x8&, p16x8&, p16x8&) { emu::lgkm_wait(N); }
@@ -340,14 +500,14 @@ template <int N> __device__ __forceinline__ void lds_wait(p16x8&, p16x8&, p16x8&
 template <int N>
 __device__ __forceinline__ void lds_wait(p16x8&, p16x8&, p16x8&, p16x8&, p16x8&, p16x8&, p16x8&, p16x8&) { emu::lgkm_wait(N); }
 #else
-// `lds_addr` = 32-bit LDS byte address (lds_addr_of), IMM = compile-time byte offset < 65536
-template <int IMM> __device__ __forceinline__ void lds_read16(p16x8& dst, uint32_t lds_addr) {
+typedef uint32_t LdsAddr;
+template <int IMM> __device__ __forceinline__ void lds_read16(p16x8& dst, LdsAddr lds_addr) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(lds_addr), "i"(IMM));
 }
 // IN-PLACE flavour (cf. gload16_refill): the slot's old value stays live in these very registers up to this read, so a ring of
 // such slots is pinned to its registers and no MFMA result is ever allocated where a fragment read lands next (an MFMA write
 // followed by an LDS write of the same VGPR is a wait-state hazard hipcc does not pad for inline asm: tools/hazard_audit.py rule B)
-template <int IMM> __device__ __forceinline__ void lds_refill16(p16x8& slot, uint32_t lds_addr) {
+template <int IMM> __device__ __forceinline__ void lds_refill16(p16x8& slot, LdsAddr lds_addr) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(slot) : "v"(lds_addr), "i"(IMM));
 }
 template <int N> __device__ __forceinline__ void lds_wait(p16x8& a, p16x8& b) {
@@ -367,7 +527,7 @@ template <int N>
 __device__ __forceinline__ void lds_wait(p16x8& a, p16x8& b, p16x8& c, p16x8& d, p16x8& e, p16x8& f) {
   asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f) : "i"(N));
 }
-__device__ __forceinline__ uint32_t lds_addr_of(const void* p) {
+__device__ __forceinline__ LdsAddr lds_addr_of(const void* p) {
   return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
 }
 #endif
@@ -510,6 +670,38 @@ __device__ __forceinline__ void clip_load8_async(u32x2& dst, const ClipWin& w, u
   emu::vm_issue(&dst, in ? static_cast<const void*>(w.base + off) : static_cast<const void*>(zeros), 8, true);
 #else
   asm volatile("buffer_load_dwordx2 %0, %1, %2, 0 offen" : "=&v"(dst) : "v"(off), "s"(w.d) : "memory");
+#endif
+}
+
+// The bare counted wait: s_waitcnt vmcnt(N), N <= 63, naming no registers (wait_vmem_upto's builtin form stops at 15).  For queues
+// whose entries are not register loads: LDS-DMA pieces, and stores (below).
+template <int N> __device__ __forceinline__ void vmem_wait_bare() {
+#ifdef MDM_EMU
+  emu::vm_wait(N);
+#else
+  asm volatile("s_waitcnt vmcnt(%0)" : : "i"(N) : "memory");
+#endif
+}
+// Do stores count in vmcnt?  On gfx9 they do, so a counted wait that lets stores stay in flight adds them to its N.  The emulator's
+// queue holds the untracked operations only -- LDS-DMA pieces, untracked loads; compiler-tracked loads and stores take effect at
+// once there -- so the same wait counts none: N = pieces + kStoresInVmcnt * stores.
+#ifdef MDM_EMU
+constexpr int kStoresInVmcnt = 0;
+#else
+constexpr int kStoresInVmcnt = 1;
+#endif
+// split4_store whose two 8-byte plane stores are COUNTED by a later vmem_wait_bare: they are issued from inline asm, one
+// instruction per plane, so that the count cannot follow a compiler decision to merge, split or reorder them (the C++
+// form relied on hipcc emitting exactly two 8-byte stores per call).
+__device__ __forceinline__ void split4_store_counted(p16_t* hi_p, p16_t* lo_p, float4 v) {
+#ifdef MDM_EMU
+  split4_store(hi_p, lo_p, v);
+#else
+  uint32_t h01, l01, h23, l23;
+  split2_p16(v.x, v.y, h01, l01);
+  split2_p16(v.z, v.w, h23, l23);
+  asm volatile("global_store_dwordx2 %0, %1, off" : : "v"(hi_p), "v"(u32x2{h01, h23}) : "memory");
+  asm volatile("global_store_dwordx2 %0, %1, off" : : "v"(lo_p), "v"(u32x2{l01, l23}) : "memory");
 #endif
 }
 

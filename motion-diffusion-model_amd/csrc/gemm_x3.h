@@ -163,21 +163,13 @@ constexpr bool x3_has_col_scale(int act, int res) { return act == 0 && (res == 0
 // A/B 0.35 % SLOWER over the whole sampling loop, profiles/r03c_ab.md; not kept.)
 __device__ __forceinline__ float gelu_erf_fast(float x) {
   const float z = fabsf(x) * 0.70710678118654752440f;
-#ifdef MDM_EMU
-  const float t = 1.0f / (1.0f + 0.3275911f * z);
-#else
-  const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * z);  // v_rcp_f32 (1 ulp) instead of the ~10-instruction IEEE divide
-#endif
+  const float t = rcp_fast(1.0f + 0.3275911f * z);
   float p = 1.061405429f;
   p = p * t - 1.453152027f;
   p = p * t + 1.421413741f;
   p = p * t - 0.284496736f;
   p = p * t + 0.254829592f;
-#ifdef MDM_EMU
-  const float erfc_z = p * t * expf(-z * z);
-#else
-  const float erfc_z = p * t * __expf(-z * z);
-#endif
+  const float erfc_z = p * t * exp_fast(-z * z);
   const float erf_abs = 1.0f - erfc_z;
   return 0.5f * x * (1.0f + copysignf(erf_abs, x));
 }
@@ -282,11 +274,7 @@ __global__ __launch_bounds__(64 * X3_NWAVE, 2) void gemm_x3_kernel(X3Operand A, 
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-#ifdef MDM_EMU
-  const int wid = tid >> 6;
-#else
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-#endif
+  const int wid = wave_index(tid);
   const int r = lane & 31, h = lane >> 5;
   const int nk = K / X3_BK;
   const int gstride = (int)gridDim.x;
@@ -358,9 +346,7 @@ __global__ __launch_bounds__(64 * X3_NWAVE, 2) void gemm_x3_kernel(X3Operand A, 
   // 16-row sub-tile (T16): lane -> (row 192 + (lane&15), k chunk lane>>4)
   const int r16 = lane & 15, g16 = lane >> 4;
   const int fa16 = (192 + r16) * 64 + ((g16 ^ x3_swz((r16 >> 2) & 3)) * 16);
-#ifndef MDM_EMU
-  const uint32_t lds_base = lds_addr_of(lds);
-#endif
+  const LdsAddr lds_base = lds_addr_of(lds);
 
   int v = (int)blockIdx.x;
   if (v >= total) return;
@@ -521,11 +507,7 @@ __global__ __launch_bounds__(64 * X3_NWAVE, 2) void gemm_x3_kernel(X3Operand A, 
           m2 += sraw[(tid * ep.stat_parts + p) * 2 + 1] + pcols * dm * dm;
         }
         const float var = m2 * ep.inv_dim;
-#ifdef MDM_EMU
-        stab[tid] = pad_row ? make_float2(0.f, 0.f) : make_float2(mean, 1.0f / sqrtf(var + 1e-5f));
-#else
-        stab[tid] = pad_row ? make_float2(0.f, 0.f) : make_float2(mean, __builtin_amdgcn_rsqf(var + 1e-5f));   // v_rsq_f32, 1 ulp
-#endif
+        stab[tid] = pad_row ? make_float2(0.f, 0.f) : make_float2(mean, rsqrt_fast(var + 1e-5f));
       }
       // the NEXT tile's partials are requested BEHIND the table build: hipcc drains the vector-memory queue in front of the
       // build's LDS reads (an LDS-DMA may be pending), and issued first, this request -- a fresh HBM / L2 round trip -- was what
@@ -563,18 +545,11 @@ __global__ __launch_bounds__(64 * X3_NWAVE, 2) void gemm_x3_kernel(X3Operand A, 
       auto slot = [](int e) constexpr { return e == NE - 1 ? RING : e % RING; };
       //   * the ring is read IN PLACE (common.h lds_refill16): its registers are never an MFMA destination
       p16x8 ah[RING + 1] = {}, al[RING + 1] = {};
-#ifndef MDM_EMU
-      const uint32_t lane_a = lds_base + fa16 - 192 * 64;   // slice s: + s * 1024 (the swizzle x3_swz((row >> 2) & 3) does not depend on s)
-#endif
+      const LdsAddr lane_a = lds_base + fa16 - 192 * 64;   // slice s: + s * 1024 (the swizzle x3_swz((row >> 2) & 3) does not depend on s)
       auto issue_reads = [&](auto e_tag, uint32_t stg) __attribute__((always_inline)) {
         constexpr int e = decltype(e_tag)::value;
-#ifdef MDM_EMU
-        lds_refill16(ah[slot(e)], lds + stg * X3_A_STAGE, fa16 - 192 * 64 + e * 1024);
-        lds_refill16(al[slot(e)], lds + stg * X3_A_STAGE, X3_A_BYTES + fa16 - 192 * 64 + e * 1024);
-#else
         lds_refill16<e * 1024>(ah[slot(e)], lane_a + stg * X3_A_STAGE);
         lds_refill16<X3_A_BYTES + e * 1024>(al[slot(e)], lane_a + stg * X3_A_STAGE);
-#endif
       };
       auto pipe_step = [&](auto par_tag) __attribute__((always_inline)) {
         constexpr int PAR = decltype(par_tag)::value, W0 = 2 * PAR, W1 = 2 * PAR + 1;
@@ -654,27 +629,17 @@ __global__ __launch_bounds__(64 * X3_NWAVE, 2) void gemm_x3_kernel(X3Operand A, 
       // flight) retires unit u's, then its 3 MFMAs go.  One LDS-DMA piece of A(g+1) rides behind each of the first four.
       constexpr int DEPTH = 2, RING = DEPTH + 1;  // fragment-read lookahead in units
       p16x8 ah[RING], al[RING];
-#ifdef MDM_EMU
-      const unsigned char* sa = lds + abuf * X3_A_STAGE;
-#define X3_RD_A(dst, plane, t, ks) lds_read16(dst, sa, (plane) * X3_A_BYTES + fa + (t) * 2048 + ((((ks) * 2 + h) ^ sw) * 16))
-#else
       // per-lane LDS byte addresses of this stage's fragments for k sub-step 0 / 1 (the XOR swizzle moves with ks)
-      const uint32_t sa0 = lds_base + abuf * X3_A_STAGE + fa;
-      const uint32_t aaddr[2] = {sa0 + ((h ^ sw) * 16), sa0 + (((2 + h) ^ sw) * 16)};
+      const LdsAddr sa0 = lds_base + abuf * X3_A_STAGE + fa;
+      const LdsAddr aaddr[2] = {sa0 + ((h ^ sw) * 16), sa0 + (((2 + h) ^ sw) * 16)};
 #define X3_RD_A(dst, plane, t, ks) lds_read16<(plane) * X3_A_BYTES + (t) * 2048>(dst, aaddr[ks])
-#endif
       // T16: the 16-row sub-tile's A fragments (one per plane covers the whole 32-deep step) are read FIRST, so they are
       // older than every unit's reads and retired by unit 0's wait; its W fragments come from wh / wl by lane swaps
       p16x8 a16h, a16l, w16h[2], w16l[2];
       if constexpr (T16) {
-#ifdef MDM_EMU
-        lds_read16(a16h, sa, fa16);
-        lds_read16(a16l, sa, X3_A_BYTES + fa16);
-#else
-        const uint32_t a16addr = lds_base + abuf * X3_A_STAGE + fa16;
+        const LdsAddr a16addr = lds_base + abuf * X3_A_STAGE + fa16;
         lds_read16<0>(a16h, a16addr);
         lds_read16<X3_A_BYTES>(a16l, a16addr);
-#endif
         w16h[0] = wh[0]; w16h[1] = wh[1];
         w16l[0] = wl[0]; w16l[1] = wl[1];
         frag32_to_frag16(w16h[0], w16h[1]);
@@ -749,9 +714,7 @@ __global__ __launch_bounds__(64 * X3_NWAVE, 2) void gemm_x3_kernel(X3Operand A, 
         // block: hipcc schedules 21 of the 28 instantiations differently for the block, and every measurement of this kernel
         // was taken on this form.)
     int lane_e = lane;
-#ifndef MDM_EMU
-    asm volatile("" : "+v"(lane_e));
-#endif
+    opaque_v(lane_e);
     const int r = lane_e & 31, h = lane_e >> 5, r16 = lane_e & 15, g16 = lane_e >> 4;
     const int m_end = min(M, m0 + rows_per_tile);
     float* patch = reinterpret_cast<float*>(lds + x3_patch_base(RINGN)) + wid * (X3_PATCH_BYTES / 4);  // [8][32] fp32
@@ -835,11 +798,9 @@ __global__ __launch_bounds__(64 * X3_NWAVE, 2) void gemm_x3_kernel(X3Operand A, 
       // stored in the last sub-tile (masking every round cost 112 hoisted lane masks, 280 spilled SGPRs).
       const int Dm = ep.D, SPq = ep.qkv.SP, Hq = ep.qkv.H;
       int ncol_e = ncol0, m0_e = m0;
-#ifndef MDM_EMU
       // opaque copies: keeps hipcc from computing the epilogue's 64-bit store addresses BEFORE the k-loop and carrying
       // them (spilled) across it
-      asm volatile("" : "+s"(ncol_e), "+s"(m0_e));
-#endif
+      opaque_s(ncol_e, m0_e);
       const int which = ncol_e / Dm, hcol = ncol_e - which * Dm, head = hcol >> 7, d0 = hcol & 127;
       const size_t shq = (size_t)(m0_e / rows_per_tile) * Hq + head;
       if (ncol0 < N) {
@@ -998,9 +959,7 @@ __global__ __launch_bounds__(64 * X3_NWAVE, 2) void gemm_x3_kernel(X3Operand A, 
       ClipWin w_oh = {}, w_ol = {}, w_rh = {}, w_rl = {};
       {
         int m0_e = m0;
-#ifndef MDM_EMU
-        asm volatile("" : "+s"(m0_e));   // (opaque: keeps the windows from being built, and carried, in front of the k-loop)
-#endif
+        opaque_s(m0_e);   // (opaque: keeps the windows from being built, and carried, in front of the k-loop)
         const size_t row0 = (size_t)m0_e * ep.ld;
         if constexpr (CLIP_OUT) {
           const uint32_t bytes = (uint32_t)(m_end - m0_e) * pitch2;
@@ -1141,20 +1100,8 @@ inline int x3_rows_per_tile(int M, int seq_len) {
 
 // persistent grid: one workgroup per CU
 inline int x3_grid_limit() {
-#ifdef MDM_EMU
-  return 3;  // small, so that the emulator exercises the tile roll-over paths
-#else
-  static int cus_of[kMaxDevices] = {};   // per device ordinal: a process may drive several GPUs
-  const int dev = rt_device_ordinal();
-  int& cus = cus_of[dev];
-  if (cus == 0) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  const int wgs = cus / 8 * 8;  // xcd_remap keeps a workgroup on one XCD only if the stride is a multiple of 8
-  return wgs > 0 ? wgs : 8;
-#endif
+  const int cus = rt_cu_count();   // (the emulator's 3 comes back as it is: a grid that small walks through the tile roll-over paths)
+  return cus >= 8 ? cus / 8 * 8 : cus;  // xcd_remap keeps a workgroup on one XCD only if the stride is a multiple of 8
 }
 
 template <int ACT, int RES, unsigned FLAGS>
@@ -1170,12 +1117,10 @@ inline int launch_gemm_x3_w(const X3Operand& A, const X3Weights& W, const X3Epil
   if (PAIR && (rpt + 1 > X3_TM - 16 || ep.pair_B < 1 || M != ep.pair_B * rpt)) return -2;   // tile row S must exist; one tile per sample
   if (PIPE && (K / X3_BK) % 2 != 0) return -2;   // the pipelined k-loop is unrolled over step pairs
   if (!x3_has_col_scale(ACT, RES) && ep.scale_cols > 0) return -2;   // (this instantiation compiles the column scale out)
-#ifndef MDM_EMU
   {   // every form needs more than the 64 KB a kernel gets unasked
     static bool configured[kMaxDevices] = {};  // per instantiation and device (the attribute belongs to the device's code object)
     if (const int rc = rt_dyn_lds_once(kfn, x3_lds_bytes(LN, RINGN), configured, stream)) return rc;
   }
-#endif
   const int grid = std::min(total, x3_grid_limit());
   MDM_LAUNCH(kfn, dim3(grid), dim3(64 * X3_NWAVE), x3_lds_bytes(LN, RINGN), stream, A, W, ep, M, N, K, rpt, tiles_n, total);
   return 0;

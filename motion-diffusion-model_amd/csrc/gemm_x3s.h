@@ -46,20 +46,15 @@ static_assert(x3s_lds_bytes(1, 18, false) == 42240 && x3s_lds_bytes(2, 18, false
 // output form, X3_FOLD, X3_OSTAT and X3_EMBED exist here -- the tile-form bits belong to the other kernel.
 // Rows are GROUPED (group_rows = tokens of a sequence; InputProcess: frames of a sample): a tile never straddles two groups, so
 // that the in_proj epilogue's (sequence, token) and the EMBED epilogue's (sample, frame) are tile-uniform / row-affine.
-#if defined(MDM_PROBES) && !defined(MDM_EMU)
-// PROBE BUILD ONLY: wave 0's shader-clock stamps of ONE selected launch (mdm_debug_set(9, n): the n-th gemm_x3s launch after the
-// call; mdm_debug_get(100 + 4 * workgroup + i)): i = 0 kernel entry, 1 chunk 0 visible to the workgroup (first barrier passed),
+// PROBE BUILD ONLY (common.h, timeline probes): mdm_debug_set(9, n): the n-th gemm_x3s launch after the call;
+// mdm_debug_get(100 + 4 * workgroup + i): i = 0 kernel entry, 1 chunk 0 visible to the workgroup (first barrier passed),
 // 2 k-loop and its trailing re-fetches retired, 3 last store issued.  tools/x3s_timeline.py
+#ifdef MDM_PROBES
 constexpr int X3S_TL_WGS = 4096;
 __device__ unsigned long long g_x3s_tl[4 * X3S_TL_WGS];
 __device__ int g_x3s_tl_on;
-#define X3S_STAMP(i)                                                                                     \
-  do {                                                                                                   \
-    if (tl_on && tid == 0 && blockIdx.x < X3S_TL_WGS) g_x3s_tl[4 * blockIdx.x + (i)] = __builtin_readcyclecounter(); \
-  } while (0)
-#else
-#define X3S_STAMP(i) do { } while (0)
 #endif
+#define X3S_STAMP(i) MDM_TL_STAMP(g_x3s_tl, X3S_TL_WGS, 4, i)
 
 template <int RT, int NSUB, bool MULTI, int ACT, int RES, unsigned FLAGS>
 __global__ __launch_bounds__(64 * X3S_WAVES, 2) void gemm_x3s_kernel(X3Operand A, X3Weights W, X3Epilogue ep, int M, int N, int K,
@@ -85,17 +80,11 @@ __global__ __launch_bounds__(64 * X3S_WAVES, 2) void gemm_x3s_kernel(X3Operand A
   constexpr bool LN_TABS = FOLD || RES == 3;
 
   const int tid = threadIdx.x;
-#if defined(MDM_PROBES) && !defined(MDM_EMU)
-  const bool tl_on = g_x3s_tl_on != 0;
-#endif
+  MDM_TL_BEGIN(g_x3s_tl_on);
   X3S_STAMP(0);
   MDM_KERNARGS_NOW("s"(A.hi), "s"(A.lo), "s"(W.hi), "s"(W.lo), "s"(M), "s"(N), "s"(K), "s"(group_rows), "s"(tiles_per_group), "s"(tiles_n), "s"(total));
   const int lane = tid & 63;
-#ifdef MDM_EMU
-  const int wid = tid >> 6;
-#else
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-#endif
+  const int wid = wave_index(tid);
   const int r = lane & 31, h = lane >> 5;
 
   const int lid = xcd_remap((int)blockIdx.x, total);
@@ -247,24 +236,17 @@ __global__ __launch_bounds__(64 * X3S_WAVES, 2) void gemm_x3s_kernel(X3Operand A
   // fragment read addresses: row r of sub-tile t, 16-byte chunk (ks * 2 + h) ^ sw of its 64-byte row
   const int sw = (r >> 2) & 3;
   const uint32_t fr0 = (uint32_t)(r * 64 + ((h ^ sw) * 16)), fr1 = (uint32_t)(r * 64 + (((2 + h) ^ sw) * 16));
-#ifndef MDM_EMU
-  const uint32_t lds_base = lds_addr_of(lds);
-#endif
+  const LdsAddr lds_base = lds_addr_of(lds);
   p16x8 fah[2][RT], fal[2][RT];      // fragments of sub-steps j (set j & 1)
   auto read_frags = [&](auto j_tag, int buf) __attribute__((always_inline)) {
     constexpr int j = decltype(j_tag)::value, ms = j / 2, ks = j % 2;
 #pragma unroll
     for (int t = 0; t < RT; ++t) {
-#ifdef MDM_EMU
-      lds_read16(fah[j & 1][t], lds + buf * BUF, (uint32_t)(((ms * 2 + 0) * 2 * RT) * 1024 + t * 2048) + (ks ? fr1 : fr0));
-      lds_read16(fal[j & 1][t], lds + buf * BUF, (uint32_t)(((ms * 2 + 1) * 2 * RT) * 1024 + t * 2048) + (ks ? fr1 : fr0));
-#else
       // (the immediate of a DS instruction is 16 bits: the part of a 64 / 72 KB chunk image beyond 32 KB goes into the address)
       constexpr uint32_t OH = (uint32_t)(((ms * 2 + 0) * 2 * RT) * 1024), OL = (uint32_t)(((ms * 2 + 1) * 2 * RT) * 1024);
-      const uint32_t ad = lds_base + (uint32_t)buf * BUF + (ks ? fr1 : fr0) + (uint32_t)t * 2048u;
+      const LdsAddr ad = lds_base + (uint32_t)buf * BUF + (ks ? fr1 : fr0) + (uint32_t)t * 2048u;
       lds_read16<(int)(OH & 32767u)>(fah[j & 1][t], ad + (OH & ~32767u));
       lds_read16<(int)(OL & 32767u)>(fal[j & 1][t], ad + (OL & ~32767u));
-#endif
     }
   };
   auto wait_frags = [&](auto j_tag, auto younger_tag) __attribute__((always_inline)) {
@@ -507,9 +489,8 @@ __global__ __launch_bounds__(64 * X3S_WAVES, 2) void gemm_x3s_kernel(X3Operand A
 // merges.  By size: 32-row tiles up to 12 sequences (B <= 6 under guidance: 22.0 vs 26.5 ms per 50-step loop at B = 1, 30.7 vs
 // 32.4 at B = 5, 36.2 vs 37.4 at B = 6), 64-row tiles above (39.2 vs 42.1 at B = 8, 61.9 vs 72.5 at B = 16; r4lat8); always
 // 128 columns (X3S_TN).
-#if defined(MDM_PROBES) && !defined(MDM_EMU)
-inline int& x3s_tl_target() { static int v = -1; return v; }   // mdm_debug_set(9, n); < 0: off
-inline int& x3s_tl_count() { static int v = 0; return v; }
+#ifdef MDM_PROBES
+inline TimelineSel& x3s_tl_sel() { static TimelineSel v; return v; }   // mdm_debug_set(9, n)
 #endif
 struct X3sOptions { int max_seqs = 80; int row_tiles = 0; };
 struct X3sShape { int rt; };
@@ -526,20 +507,17 @@ inline int launch_gemm_x3s_t(const X3Operand& A, const X3Weights& W, const X3Epi
   if (!x3_has_col_scale(ACT, RES) && ep.scale_cols > 0) return -2;
   if ((FLAGS & X3_OSTAT) != 0 && N % X3S_TN != 0) return -2;
   constexpr int LDS = x3s_lds_bytes(RT, NSUB, MULTI);
-#ifndef MDM_EMU
   if (LDS > 65536) {
     static bool configured[kMaxDevices] = {};
     if (const int rc = rt_dyn_lds_once(kfn, LDS, configured, stream)) return rc;
   }
-#endif
   const int TR = 32 * RT, TN = X3S_TN;
   const int tpg = (group_rows + TR - 1) / TR, tiles_m = (M / group_rows) * tpg, tiles_n = (N + TN - 1) / TN;
   const int total = tiles_m * tiles_n;
-#if defined(MDM_PROBES) && !defined(MDM_EMU)
-  if (x3s_tl_target() >= 0) {   // timeline probe: stamps on for exactly the selected launch (stream-ordered switch)
-    static int on_v[2] = {0, 1};
-    const int on = (x3s_tl_count()++ == x3s_tl_target()) ? 1 : 0;
-    if (hipMemcpyToSymbolAsync(HIP_SYMBOL(g_x3s_tl_on), &on_v[on], sizeof(int), 0, hipMemcpyHostToDevice, stream) != hipSuccess) return -1;
+#ifdef MDM_PROBES
+  {
+    bool on = false;
+    if (rt_timeline_switch(x3s_tl_sel(), g_x3s_tl_on, stream, &on)) return -1;
     if (on) fprintf(stderr, "[x3s timeline] launch: RT %d NSUB %d ACT %d RES %d F32 %d PLANES %d QKV %d FOLD %d OSTAT %d | M %d N %d K %d group_rows %d workgroups %d\n",
                     RT, NSUB, ACT, RES, (int)((FLAGS & X3_OUT_F32) != 0), (int)((FLAGS & X3_OUT_PLANES) != 0), (int)((FLAGS & X3_OUT_QKV) != 0),
                     (int)((FLAGS & X3_FOLD) != 0), (int)((FLAGS & X3_OSTAT) != 0), M, N, K, group_rows, total);

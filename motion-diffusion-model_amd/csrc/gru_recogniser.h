@@ -31,24 +31,6 @@ namespace mdm {
 constexpr int GRU_SEQ_ROWS = 16;        // sequences per workgroup of gru_seq_kernel, at every batch size
 constexpr int GRU_TAIL_MAX = 64;        // linear1's width (30) and num_class are run-time values up to this
 
-// v_mfma_f32_16x16x4_f32: lane l supplies A[i = l&15][k = l>>4] and B[k = l>>4][j = l&15]; D[reg] is row 4 (l>>4) + reg, column l&15.
-// 32 cycles per SIMD, 40 dependent: the three gate accumulators of a wave alternate.
-__device__ __forceinline__ f32x4 mfma16_f32(float a, float b, f32x4 c) {
-#ifdef MDM_EMU
-  const int l = emu::lane_id(), j = l & 15, q = l >> 4;
-  float bk[4];
-  for (int k = 0; k < 4; ++k) bk[k] = emu::shfl_f32(b, j + 16 * k);
-  for (int r = 0; r < 4; ++r) {
-    float acc = c[r];
-    for (int k = 0; k < 4; ++k) acc = fmaf(emu::shfl_f32(a, 4 * q + r + 16 * k), bk[k], acc);      // k ascending
-    c[r] = acc;
-  }
-  return c;
-#else
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-#endif
-}
-
 // A operand of layer 0's input projection over x [B][I][T] (T contiguous): logical row m = b T + t, logical k = feature ->
 // x[b][k][t], zero for k >= I.  Consecutive threads take consecutive rows (frames): 4-byte loads, coalesced along t.
 struct GruFrameLoader {

@@ -180,15 +180,8 @@ int mdm_sample_loop_dec(mdm_model_t* m, const mdm_sample_dec_params_t* pd, float
   }
 #endif
   hipStream_t gs[AuxStreams::kMax + 1] = {s, s, s, s};
-#if !defined(MDM_EMU) && defined(MDM_PROBES)
-  if (G > 1) {
-    if (int rc = m->aux.ensure(G - 1)) return rc;
-    if (hipEventRecord(m->aux.fork, s) != hipSuccess) return fail(MDM_EHIP, "mdm_sample_loop_dec: hipEventRecord failed");
-    for (int g = 1; g < G; ++g) {
-      gs[g] = m->aux.s[g - 1];
-      if (hipStreamWaitEvent(gs[g], m->aux.fork, 0) != hipSuccess) return fail(MDM_EHIP, "mdm_sample_loop_dec: hipStreamWaitEvent failed");
-    }
-  }
+#ifdef MDM_PROBES
+  if (int rc = m->aux.fork_from(s, G, gs)) return rc;
 #endif
   const int Bg = B / G, nseq_g = nbranch * Bg, S = m->cfg.context_len + P;
   const size_t Mg = (size_t)nseq_g * S, FFs = m->cfg.ff_size;
@@ -240,10 +233,8 @@ int mdm_sample_loop_dec(mdm_model_t* m, const mdm_sample_dec_params_t* pd, float
     }
     if (dump) ++dump_i;
   }
-#if !defined(MDM_EMU) && defined(MDM_PROBES)
-  for (int g = 1; g < G; ++g)   // join, also on the error path: the caller's stream must not run ahead of the side streams
-    if (hipEventRecord(m->aux.join[g - 1], gs[g]) != hipSuccess || hipStreamWaitEvent(s, m->aux.join[g - 1], 0) != hipSuccess)
-      return fail(MDM_EHIP, "mdm_sample_loop_dec: joining the side streams failed");
+#ifdef MDM_PROBES
+  if (int rc = m->aux.join_into(s, G, gs)) return rc;   // also on the error path: the caller's stream must not run ahead of the side streams
 #endif
   return rc_loop;
 }

@@ -66,13 +66,7 @@ const char* mdm_build_info(void) {
 #else
          "0"
 #endif
-         ";emu="
-#ifdef MDM_EMU
-         "1"
-#else
-         "0"
-#endif
-         ";planes=f16";
+         ";emu=" MDM_BUILD_INFO_EMU ";planes=f16";
 }
 const char* mdm_last_error(void) { return g_err.c_str(); }
 
@@ -198,17 +192,7 @@ int mdm_profile_read(mdm_model_t* m, int32_t category, double* total_ms, int64_t
   if (m == nullptr || category < 0 || category >= MDM_PROF_NUM) return fail(MDM_EINVAL, "mdm_profile_read: bad argument");
   double ms = 0.0, fl = 0.0;
   int64_t n = 0;
-#ifndef MDM_EMU
-  for (const auto& r : m->prof.recs) {
-    if (r.cat != category) continue;
-    if (hipEventSynchronize(r.b) != hipSuccess) return fail(MDM_EHIP, "mdm_profile_read: hipEventSynchronize failed");
-    float dt = 0.f;
-    if (hipEventElapsedTime(&dt, r.a, r.b) != hipSuccess) return fail(MDM_EHIP, "mdm_profile_read: hipEventElapsedTime failed");
-    ms += dt; fl += r.flops; ++n;
-  }
-#else
-  n = m->prof.launches[category];
-#endif
+  if (int rc = m->prof.read(category, ms, n, fl)) return rc;
   if (total_ms) *total_ms = ms;
   if (launches) *launches = n;
   if (flops) *flops = fl;
@@ -217,12 +201,7 @@ int mdm_profile_read(mdm_model_t* m, int32_t category, double* total_ms, int64_t
 
 int mdm_profile_reset(mdm_model_t* m) {
   if (m == nullptr) return fail(MDM_EINVAL, "mdm_profile_reset: null model");
-#ifndef MDM_EMU
-  for (auto& r : m->prof.recs) { m->prof.pool.push_back(r.a); m->prof.pool.push_back(r.b); }
-  m->prof.recs.clear();
-#else
-  for (auto& c : m->prof.launches) c = 0;
-#endif
+  m->prof.reset();
   return MDM_OK;
 }
 

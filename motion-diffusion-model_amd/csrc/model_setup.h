@@ -210,11 +210,7 @@ int fold_layernorm(const mdm_model* m, const float* w, const float* bias, const 
 // Range flag, the padded poseEmbedding weight and the time table
 int prepare_tables(const mdm_model* m, hipStream_t s) {
   const int D = m->cfg.latent_dim, R = m->cfg.max_len;
-#ifdef MDM_EMU
-  *m->range_flag = 0;
-#else
-  if (hipMemsetAsync(m->range_flag, 0, 4, s) != hipSuccess) return fail(MDM_EHIP, "mdm_prepare: hipMemsetAsync failed");
-#endif
+  if (int rc = rt_zero(m->range_flag, 4, s)) return rc;
   MDM_LAUNCH(pad_rows_kernel, dim3(256), dim3(256), 0, s, m->w_in_pad, m->W("input_process.poseEmbedding.weight"), D,
              m->jf, m->jf_pad);
   if (int rc = rt_launch_status()) return rc;
@@ -327,14 +323,7 @@ int mdm_weights_in_range(mdm_model_t* m, int32_t* in_range, void* stream) {
   if (int rc = check_ready(m)) return rc;
   if (in_range == nullptr) return fail(MDM_EINVAL, "mdm_weights_in_range: null argument");
   int flag = 0;
-#ifdef MDM_EMU
-  (void)stream;
-  flag = *m->range_flag;
-#else
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemcpyAsync(&flag, m->range_flag, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-    return fail(MDM_EHIP, "mdm_weights_in_range: reading the flag back failed");
-#endif
+  if (int rc = rt_read_back(&flag, m->range_flag, 4, static_cast<hipStream_t>(stream))) return rc;
   *in_range = flag == 0 ? 1 : 0;
   return MDM_OK;
 }

@@ -15,49 +15,31 @@ int mdm_debug_set(int what, int value) {
   if (what == 1) g_x3_reuse_planes = value;
   if (what == 4) g_f6_reference = value;
   if (what == 5) g_f6_linear = value;
-#ifndef MDM_EMU
-  if (what == 9) { x3s_tl_target() = value; x3s_tl_count() = 0; }   // gemm_x3s.h timeline probe: stamp the value-th launch from now
-  if (what == 10) { xb_tl_target() = value; xb_tl_count() = 0; }    // xattn_block.h timeline probe
-  if (what == 11) { sb_tl_target() = value; sb_tl_count() = 0; }    // selfattn_block.h timeline probe (self and cross launches)
-#endif
+  // the timeline probes (common.h): stamp the value-th launch from now of gemm_x3s.h / xattn_block.h / selfattn_block.h (self and cross)
+  if (what == 9) x3s_tl_sel() = TimelineSel{value, 0};
+  if (what == 10) xb_tl_sel() = TimelineSel{value, 0};
+  if (what == 11) sb_tl_sel() = TimelineSel{value, 0};
   return MDM_OK;
 }
 
-int mdm_debug_get(int idx, double* out) {   // timeline stamps of the x3s / xattn / selfattn probes
-#ifndef MDM_EMU
-  if (idx >= 300000) {   // selfattn_block.h timeline stamps (read once at idx == 300000, then served from the host copy)
-    static std::vector<unsigned long long> tl(8 * SB_TL_WGS);
-    if (idx - 300000 >= 8 * SB_TL_WGS || out == nullptr) return fail(MDM_EINVAL, "mdm_debug_get: bad timeline index");
-    if (idx == 300000 && (hipDeviceSynchronize() != hipSuccess ||
-                          hipMemcpyFromSymbol(tl.data(), HIP_SYMBOL(g_sb_tl), tl.size() * sizeof(unsigned long long)) != hipSuccess))
-      return fail(MDM_EHIP, "mdm_debug_get: reading the timeline failed");
-    *out = (double)tl[idx - 300000];
-    return MDM_OK;
-  }
-  if (idx >= 200000) {   // xattn_block.h timeline stamps (read once at idx == 200000, then served from the host copy)
-    static std::vector<unsigned long long> tl(8 * XB_TL_WGS);
-    if (idx - 200000 >= 8 * XB_TL_WGS || out == nullptr) return fail(MDM_EINVAL, "mdm_debug_get: bad timeline index");
-    if (idx == 200000 && (hipDeviceSynchronize() != hipSuccess ||
-                          hipMemcpyFromSymbol(tl.data(), HIP_SYMBOL(g_xb_tl), tl.size() * sizeof(unsigned long long)) != hipSuccess))
-      return fail(MDM_EHIP, "mdm_debug_get: reading the timeline failed");
-    *out = (double)tl[idx - 200000];
-    return MDM_OK;
-  }
-  if (idx >= 100) {   // gemm_x3s.h timeline stamps (read once at idx == 100, then served from the host copy)
-    static std::vector<unsigned long long> tl(4 * X3S_TL_WGS);
-    if (idx - 100 >= 4 * X3S_TL_WGS || out == nullptr) return fail(MDM_EINVAL, "mdm_debug_get: bad timeline index");
-    if (idx == 100 && (hipDeviceSynchronize() != hipSuccess ||
-                       hipMemcpyFromSymbol(tl.data(), HIP_SYMBOL(g_x3s_tl), tl.size() * sizeof(unsigned long long)) != hipSuccess))
-      return fail(MDM_EHIP, "mdm_debug_get: reading the timeline failed");
-    *out = (double)tl[idx - 100];
-    return MDM_OK;
-  }
-  return fail(MDM_EINVAL, "mdm_debug_get: not a timeline index");
-#else
-  if (out != nullptr) *out = 0.0;
-  (void)idx;
+}  // extern "C"
+
+// Stamp idx - BASE of one kernel's timeline array: read to the host once, at idx == BASE, then served from that copy.
+template <int BASE, size_t N> static int timeline_get(const unsigned long long (&arr)[N], int idx, double* out) {
+  static std::vector<unsigned long long> tl(N);
+  if (idx - BASE >= (int)N || out == nullptr) return fail(MDM_EINVAL, "mdm_debug_get: bad timeline index");
+  if (idx == BASE && !rt_timeline_read(tl.data(), arr, N)) return fail(MDM_EHIP, "mdm_debug_get: reading the timeline failed");
+  *out = (double)tl[idx - BASE];
   return MDM_OK;
-#endif
+}
+
+extern "C" {
+
+int mdm_debug_get(int idx, double* out) {   // timeline stamps of the selfattn / xattn / x3s probes
+  if (idx >= 300000) return timeline_get<300000>(g_sb_tl, idx, out);
+  if (idx >= 200000) return timeline_get<200000>(g_xb_tl, idx, out);
+  if (idx >= 100) return timeline_get<100>(g_x3s_tl, idx, out);
+  return fail(MDM_EINVAL, "mdm_debug_get: not a timeline index");
 }
 
 size_t mdm_linear_f16f6_scratch_bytes(int32_t M, int32_t N, int32_t K) {

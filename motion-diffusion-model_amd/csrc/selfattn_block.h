@@ -69,20 +69,15 @@ constexpr int SB_VEC = SB_V + SB_IMG;                        // bias[384] | cols
 constexpr int SB_TAB = SB_VEC + 2 * 384 * 4;                 // (mean, rstd) of the 64 rows
 constexpr int SB_MASK = SB_TAB + SB_TR * 8;                  // additive key mask (0 / -inf) of the 64 keys
 constexpr int SB_LDS = SB_MASK + SB_TR * 4;
-#if defined(MDM_PROBES) && !defined(MDM_EMU)
-// PROBE BUILD ONLY: wave 0's shader-clock stamps of ONE selected launch (mdm_debug_set(11, n): the n-th launch of this kernel after the
-// call; mdm_debug_get(300000 + 8 * workgroup + i)): i = 0 kernel entry, 1 chunk 0 / vectors / mask visible (first barrier passed),
+// PROBE BUILD ONLY (common.h, timeline probes): mdm_debug_set(11, n): the n-th launch of this kernel after the call;
+// mdm_debug_get(300000 + 8 * workgroup + i): i = 0 kernel entry, 1 chunk 0 / vectors / mask visible (first barrier passed),
 // 2 contraction retired, 3 fragment images complete, 4 attention arithmetic done, 5 last plane store issued.
+#ifdef MDM_PROBES
 constexpr int SB_TL_WGS = 1024;
 __device__ unsigned long long g_sb_tl[8 * SB_TL_WGS];
 __device__ int g_sb_tl_on;
-#define SB_STAMP(i)                                                                                    \
-  do {                                                                                                 \
-    if (tl_on && tid == 0 && blockIdx.x < SB_TL_WGS) g_sb_tl[8 * blockIdx.x + (i)] = __builtin_readcyclecounter(); \
-  } while (0)
-#else
-#define SB_STAMP(i) do { } while (0)
 #endif
+#define SB_STAMP(i) MDM_TL_STAMP(g_sb_tl, SB_TL_WGS, 8, i)
 
 // MODE 0: self-attention, plain in_proj (layer 0); 1: self-attention, norm3 of the previous layer folded; 2: CROSS (norm1 folded)
 template <int MODE>
@@ -97,20 +92,14 @@ __global__ __launch_bounds__(64 * SB_WAVES, 1) void selfattn_block_kernel(SelfAt
                 "slot <-> sub-step map across chunks (gemm_x3s.h: NSUB > D); vmcnt range");
 
   const int tid = threadIdx.x, lane = tid & 63;
-#if defined(MDM_PROBES) && !defined(MDM_EMU)
-  const bool tl_on = g_sb_tl_on != 0;
-#endif
+  MDM_TL_BEGIN(g_sb_tl_on);
   SB_STAMP(0);
   MDM_KERNARGS_NOW("s"(a.x.hi), "s"(a.x.lo), "s"(a.w.hi), "s"(a.w.lo), "s"(a.xstat), "s"(a.bias), "s"(a.colsum), "s"(a.H), "s"(a.D), "s"(a.M), "s"(a.S), "s"(total));
   const p16_t* const xh_p = rt_sgpr_ptr(a.x.hi);
   const p16_t* const xl_p = rt_sgpr_ptr(a.x.lo);
   const float* const bias_p = rt_sgpr_ptr(a.bias);
   const float* const colsum_p = rt_sgpr_ptr(a.colsum);
-#ifdef MDM_EMU
-  const int wid = tid >> 6;
-#else
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-#endif
+  const int wid = wave_index(tid);
   const int r = lane & 31, h = lane >> 5;
   const int lid = xcd_remap((int)blockIdx.x, total);
   const int seq = lid / a.H, head = lid - seq * a.H;     // the heads of a sequence are neighbours on one XCD: they share its rows
@@ -268,23 +257,16 @@ __global__ __launch_bounds__(64 * SB_WAVES, 1) void selfattn_block_kernel(SelfAt
   // fragment read addresses (gemm_x3s.h): row r of sub-tile t, 16-byte chunk (ks * 2 + h) ^ sw of its 64-byte row
   const int sw = (r >> 2) & 3;
   const uint32_t fr0 = (uint32_t)(r * 64 + ((h ^ sw) * 16)), fr1 = (uint32_t)(r * 64 + (((2 + h) ^ sw) * 16));
-#ifndef MDM_EMU
-  const uint32_t lds_base = lds_addr_of(lds);
-#endif
+  const LdsAddr lds_base = lds_addr_of(lds);
   p16x8 fah[2][2], fal[2][2];      // fragments of sub-step j (set j & 1), row sub-tile t
   auto read_frags = [&](auto j_tag, int buf) __attribute__((always_inline)) {
     constexpr int j = decltype(j_tag)::value, ms = j / 2, ks = j % 2;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-#ifdef MDM_EMU
-      lds_read16(fah[j & 1][t], lds + buf * SB_BUF, (uint32_t)(((ms * 2 + 0) * 4) * 1024 + t * 2048) + (ks ? fr1 : fr0));
-      lds_read16(fal[j & 1][t], lds + buf * SB_BUF, (uint32_t)(((ms * 2 + 1) * 4) * 1024 + t * 2048) + (ks ? fr1 : fr0));
-#else
       constexpr uint32_t OH = (uint32_t)(((ms * 2 + 0) * 4) * 1024), OL = (uint32_t)(((ms * 2 + 1) * 4) * 1024);
-      const uint32_t ad = lds_base + (uint32_t)buf * SB_BUF + (ks ? fr1 : fr0) + (uint32_t)t * 2048u;
+      const LdsAddr ad = lds_base + (uint32_t)buf * SB_BUF + (ks ? fr1 : fr0) + (uint32_t)t * 2048u;
       lds_read16<(int)OH>(fah[j & 1][t], ad);
       lds_read16<(int)OL>(fal[j & 1][t], ad);
-#endif
     }
   };
 
@@ -447,11 +429,7 @@ __global__ __launch_bounds__(64 * SB_WAVES, 1) void selfattn_block_kernel(SelfAt
   for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-#ifdef MDM_EMU
-      const float pe = expf(p[kt][e] - mx);
-#else
-      const float pe = __expf(p[kt][e] - mx);
-#endif
+      const float pe = exp_fast(p[kt][e] - mx);
       p[kt][e] = pe;
       sum += pe;
     }
@@ -501,9 +479,8 @@ __global__ __launch_bounds__(64 * SB_WAVES, 1) void selfattn_block_kernel(SelfAt
 }
 
 #ifndef MDM_X3_KERNEL_ONLY
-#if defined(MDM_PROBES) && !defined(MDM_EMU)
-inline int& sb_tl_target() { static int v = -1; return v; }   // mdm_debug_set(11, n); < 0: off
-inline int& sb_tl_count() { static int v = 0; return v; }
+#ifdef MDM_PROBES
+inline TimelineSel& sb_tl_sel() { static TimelineSel v; return v; }   // mdm_debug_set(11, n)
 #endif
 inline bool selfattn_block_supported(int D, int S) { return S >= 1 && S <= SB_TR && D % 128 == 0 && D >= 128; }
 inline bool crossattn_block_supported(int D, int S, int ntok) { return selfattn_block_supported(D, S) && ntok >= 1 && ntok <= SB_TR; }
@@ -512,18 +489,12 @@ template <int MODE>
 inline int launch_seqhead_block_t(const SelfAttnArgs& a, hipStream_t stream) {
   auto kfn = &selfattn_block_kernel<MODE>;
   const int total = (a.M / a.S) * a.H;
-#ifndef MDM_EMU
   {
     static bool configured[kMaxDevices] = {};
     if (const int rc = rt_dyn_lds_once(kfn, SB_LDS, configured, stream)) return rc;
   }
-#endif
-#if defined(MDM_PROBES) && !defined(MDM_EMU)
-  if (sb_tl_target() >= 0) {   // timeline probe: stamps on for exactly the selected launch (stream-ordered switch)
-    static int on_v[2] = {0, 1};
-    const int on = (sb_tl_count()++ == sb_tl_target()) ? 1 : 0;
-    if (hipMemcpyToSymbolAsync(HIP_SYMBOL(g_sb_tl_on), &on_v[on], sizeof(int), 0, hipMemcpyHostToDevice, stream) != hipSuccess) return -1;
-  }
+#ifdef MDM_PROBES
+  if (rt_timeline_switch(sb_tl_sel(), g_sb_tl_on, stream)) return -1;
 #endif
   MDM_LAUNCH(kfn, dim3(total), dim3(64 * SB_WAVES), SB_LDS, stream, a, total);
   return 0;

@@ -223,35 +223,10 @@ void smf_launch_direction(const SmplifyDirArgs& a, hipStream_t s) {
   else { auto k = &smplify_direction_kernel<1024>; MDM_LAUNCH(k, dim3(1), dim3(1024), 0, s, a); }
 }
 
-// `bytes` (at most 4096) from the device to `dst` behind everything `s` holds: one copy into pinned memory and one synchronisation.
-// The 4 KB pinned buffer is allocated at a thread's first read and kept until the process ends (never freed: one per calling thread).
-int smf_read(void* dst, const void* src, size_t bytes, hipStream_t s) {
-#ifdef MDM_EMU
-  (void)s;
-  memcpy(dst, src, bytes);
-  return 0;
-#else
-  static thread_local void* pinned = nullptr;
-  if (pinned == nullptr && hipHostMalloc(&pinned, 4096, hipHostMallocDefault) != hipSuccess) {
-    pinned = nullptr;
-    return fail(MDM_EHIP, "mdm_smplify: hipHostMalloc of the 4 KB read-back buffer failed");
-  }
-  if (hipMemcpyAsync(pinned, src, bytes, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-    return fail(MDM_EHIP, "mdm_smplify: reading the reduced scalars back failed");
-  memcpy(dst, pinned, bytes);
-  return 0;
-#endif
-}
-
 int smf_refuse_capture(const std::string& f, hipStream_t s) {
-#ifndef MDM_EMU
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+  if (rt_is_capturing(s))
     return fail(MDM_EUNSUPPORTED, f + "the stream is being captured into a hipGraph -- the optimiser reads its scalars back on the host "
                 "after every evaluation, so this call cannot be captured");
-#else
-  (void)f; (void)s;
-#endif
   return 0;
 }
 
@@ -259,7 +234,7 @@ int smf_refuse_capture(const std::string& f, hipStream_t s) {
 struct SmfScalars { float loss, gmax, gd, bad; };
 int smf_read_scalars(const float* partial_dev, int nwg, hipStream_t s, SmfScalars& o) {
   float host[128 * SMF_REC];
-  if (int rc = smf_read(host, partial_dev, (size_t)nwg * SMF_REC * sizeof(float), s)) return rc;
+  if (int rc = rt_read_back(host, partial_dev, (size_t)nwg * SMF_REC * sizeof(float), s)) return rc;
   o = SmfScalars{0.f, 0.f, 0.f, 0.f};
   for (int w = 0; w < nwg; ++w) {
     o.loss += host[w * SMF_REC];
@@ -324,7 +299,7 @@ struct SmfStage {
         smf_launch_direction(da, s);
         if (int rc = rt_launch_status()) return rc;
         float rec_h[SMF_DIR_REC];
-        if (int rc = smf_read(rec_h, rec, sizeof(rec_h), s)) return rc;
+        if (int rc = rt_read_back(rec_h, rec, sizeof(rec_h), s)) return rc;
         const SmfNum gtd = smf_t32(rec_h[0]), d_norm = smf_t32(rec_h[1]);
         const double prev_loss = loss;
         if (first) t = smf_min(smf_py(1.0), smf_py(1.0) / smf_t32(rec_h[2])) * lr;

@@ -59,20 +59,15 @@ struct XattnArgs {
 };
 
 constexpr int XB_WAVES = 4, XB_TR = 32;
-#if defined(MDM_PROBES) && !defined(MDM_EMU)
-// PROBE BUILD ONLY: wave 0's shader-clock stamps of ONE selected launch (mdm_debug_set(10, n): the n-th xattn_block launch after the
-// call; mdm_debug_get(200000 + 8 * workgroup + i)): i = 0 kernel entry, 1 y image / vectors / table visible, 2 GEMM 1 retired,
+// PROBE BUILD ONLY (common.h, timeline probes): mdm_debug_set(10, n): the n-th xattn_block launch after the call;
+// mdm_debug_get(200000 + 8 * workgroup + i): i = 0 kernel entry, 1 y image / vectors / table visible, 2 GEMM 1 retired,
 // 3 q image complete, 4 attention image complete, 5 GEMM 2 retired, 6 last plane store issued, 7 statistics written.
+#ifdef MDM_PROBES
 constexpr int XB_TL_WGS = 1024;
 __device__ unsigned long long g_xb_tl[8 * XB_TL_WGS];
 __device__ int g_xb_tl_on;
-#define XB_STAMP(i)                                                                                    \
-  do {                                                                                                 \
-    if (tl_on && tid == 0 && blockIdx.x < XB_TL_WGS) g_xb_tl[8 * blockIdx.x + (i)] = __builtin_readcyclecounter(); \
-  } while (0)
-#else
-#define XB_STAMP(i) do { } while (0)
 #endif
+#define XB_STAMP(i) MDM_TL_STAMP(g_xb_tl, XB_TL_WGS, 8, i)
 constexpr int xb_img_bytes(int ncb) { return ncb * 128 * 128; }               // 32 rows x D x hi|lo x 2 B, D = 128 ncb
 constexpr int xb_vec_base(int ncb) { return 2 * xb_img_bytes(ncb); }          // five [D] fp32 vectors
 constexpr int xb_tab_base(int ncb) { return xb_vec_base(ncb) + 5 * 128 * ncb * 4; }
@@ -93,15 +88,9 @@ __global__ __launch_bounds__(64 * XB_WAVES, 1) void xattn_block_kernel(XattnArgs
   static_assert(NSUBT % 8 == 0 && 8 % WD == 0 && LW * WD <= 63, "chunks of eight sub-steps; slot <-> sub-step map; vmcnt range");
 
   const int tid = threadIdx.x, lane = tid & 63;
-#if defined(MDM_PROBES) && !defined(MDM_EMU)
-  const bool tl_on = g_xb_tl_on != 0;
-#endif
+  MDM_TL_BEGIN(g_xb_tl_on);
   XB_STAMP(0);
-#ifdef MDM_EMU
-  const int wid = tid >> 6;
-#else
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-#endif
+  const int wid = wave_index(tid);
   const int r = lane & 31, h = lane >> 5;
   const int lid = xcd_remap((int)blockIdx.x, total);
   const int grp = lid / tiles_per_group, tig = lid - grp * tiles_per_group;
@@ -176,22 +165,15 @@ __global__ __launch_bounds__(64 * XB_WAVES, 1) void xattn_block_kernel(XattnArgs
   // ---- fragment reads of the k-blocked images: row r, 16-byte chunk (ks * 2 + h) ^ sw of its 64-byte row
   const int sw = (r >> 2) & 3;
   const uint32_t fr0 = (uint32_t)(r * 64 + ((h ^ sw) * 16)), fr1 = (uint32_t)(r * 64 + (((2 + h) ^ sw) * 16));
-#ifndef MDM_EMU
-  const uint32_t lds_base = lds_addr_of(lds);
-#endif
+  const LdsAddr lds_base = lds_addr_of(lds);
   p16x8 fah[2], fal[2];
   // sub-step j (0..7) of chunk c (eight sub-steps = four k-blocks = 16 KB of image) of the image at byte offset `img_off`
   auto read_frags = [&](auto j_tag, int img_off, int c) __attribute__((always_inline)) {
     constexpr int j = decltype(j_tag)::value, ms = j / 2, ks = j % 2;
     constexpr uint32_t OH = (uint32_t)((ms * 2 + 0) * 2 * 1024), OL = (uint32_t)((ms * 2 + 1) * 2 * 1024);
-#ifdef MDM_EMU
-    lds_read16(fah[j & 1], lds + img_off + c * 16384, OH + (ks ? fr1 : fr0));
-    lds_read16(fal[j & 1], lds + img_off + c * 16384, OL + (ks ? fr1 : fr0));
-#else
-    const uint32_t ad = lds_base + (uint32_t)img_off + (uint32_t)c * 16384u + (ks ? fr1 : fr0);
+    const LdsAddr ad = lds_base + (uint32_t)img_off + (uint32_t)c * 16384u + (ks ? fr1 : fr0);
     lds_read16<(int)OH>(fah[j & 1], ad);
     lds_read16<(int)OL>(fal[j & 1], ad);
-#endif
   };
   auto wait_w = [&](auto slot_tag) __attribute__((always_inline)) {      // slot retired: younger = the other slot's loads
     constexpr int sl = decltype(slot_tag)::value;
@@ -313,11 +295,7 @@ __global__ __launch_bounds__(64 * XB_WAVES, 1) void xattn_block_kernel(XattnArgs
     for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-#ifdef MDM_EMU
-        const float pe = expf(p[kt][e] - mx);
-#else
-        const float pe = __expf(p[kt][e] - mx);
-#endif
+        const float pe = exp_fast(p[kt][e] - mx);
         p[kt][e] = pe;
         sum += pe;
       }
@@ -469,9 +447,8 @@ __global__ __launch_bounds__(64 * XB_WAVES, 1) void xattn_block_kernel(XattnArgs
 }
 
 #ifndef MDM_X3_KERNEL_ONLY
-#if defined(MDM_PROBES) && !defined(MDM_EMU)
-inline int& xb_tl_target() { static int v = -1; return v; }   // mdm_debug_set(10, n); < 0: off
-inline int& xb_tl_count() { static int v = 0; return v; }
+#ifdef MDM_PROBES
+inline TimelineSel& xb_tl_sel() { static TimelineSel v; return v; }   // mdm_debug_set(10, n)
 #endif
 inline bool xattn_block_supported(int D, int ntok) { return (D == 256 || D == 512) && ntok >= 1 && ntok <= 96; }
 
@@ -479,19 +456,13 @@ template <int NCB, int NKT>
 inline int launch_xattn_block_t(const XattnArgs& a, hipStream_t stream) {
   auto kfn = &xattn_block_kernel<NCB, NKT>;
   constexpr int LDS = xb_lds_bytes(NCB);
-#ifndef MDM_EMU
   if (LDS > 65536) {
     static bool configured[kMaxDevices] = {};
     if (const int rc = rt_dyn_lds_once(kfn, LDS, configured, stream)) return rc;
   }
-#endif
   const int tpg = (a.S + XB_TR - 1) / XB_TR, total = (a.M / a.S) * tpg;
-#if defined(MDM_PROBES) && !defined(MDM_EMU)
-  if (xb_tl_target() >= 0) {   // timeline probe: stamps on for exactly the selected launch (stream-ordered switch)
-    static int on_v[2] = {0, 1};
-    const int on = (xb_tl_count()++ == xb_tl_target()) ? 1 : 0;
-    if (hipMemcpyToSymbolAsync(HIP_SYMBOL(g_xb_tl_on), &on_v[on], sizeof(int), 0, hipMemcpyHostToDevice, stream) != hipSuccess) return -1;
-  }
+#ifdef MDM_PROBES
+  if (rt_timeline_switch(xb_tl_sel(), g_xb_tl_on, stream)) return -1;
 #endif
   MDM_LAUNCH(kfn, dim3(total), dim3(64 * XB_WAVES), LDS, stream, a, tpg, total);
   return 0;
