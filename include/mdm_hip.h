@@ -718,6 +718,9 @@ int mdm_clip_text_encode(const mdm_clip_text_model_t* model, const int32_t* ids_
 #define MDM_METRICS_GATHER_DIST 2
 #define MDM_METRICS_POLY_MMD 3
 #define MDM_METRICS_FEATURE_STATS 4
+#define MDM_METRICS_RETRIEVAL_RANKS 5
+#define MDM_METRICS_DIST_MATRIX 6
+#define MDM_METRICS_CONFUSION 7
 
 /* Bytes of workspace of the call `kind` (MDM_METRICS_*) on `rows` rows; 0 on a bad argument (mdm_last_error says which).
  * MDM_METRICS_POLY_MMD: rows = the subset size m, subsets = S; 2 S ceil(m / 64) 16 doubles plus 64 bytes; subsets * rows < 2^31 and
@@ -751,6 +754,35 @@ int mdm_poly_mmd(const float* g_dev, int32_t Ng, const float* r_dev, int32_t Nr,
  * x_dev [N, D], both in fp64.  N >= 2, D * D < 2^31.  Two launches. */
 int mdm_feature_stats(const float* x_dev, int32_t N, int32_t D, double* mu_dev, double* sigma_dev, void* workspace_dev,
                       size_t workspace_bytes, void* stream);
+
+/* ---- The metrics of the HumanML3D / KIT evaluation (data_loaders/humanml/utils/metrics.py: R-precision, matching score, the
+ * distance matrix) and the a2m family's accuracy (eval/a2m/ * /accuracy.py), on device features.  (Additive to ABI 10.)  The common
+ * rules of the five calls above hold: the same distance statement, the same refusals before any launch, the one-chain guard, no
+ * device allocation, no synchronisation, capture-safe.
+ *
+ * mdm_retrieval_ranks: q_dev (texts) and c_dev (motions) are [N, D]; group_offsets_dev [n_groups + 1] (int32, ascending, [0] == 0,
+ * [n_groups] == N) cuts the rows into the reference's batches, each of 1 .. max_group_rows rows (sizes may differ).  Row i of a group
+ * [b, e):  diag_dev[i] = sqrt(d2(q_i, c_i));  rank_dev[i] = #{j in [b, e): d2(q_i, c_j) < d2(q_i, c_i)} + #{j in [b, i): d2(q_i, c_j) ==
+ * d2(q_i, c_i)}, the position of i in a stable ascending sort of row i of the group's distance matrix (np.argsort + calculate_top_k
+ * whenever the row has no tie).  topk_count_dev[k] (int64, k < top_k, 1 <= top_k <= 16) = #{i: rank[i] <= k} (top_k_mat.sum(axis=0)
+ * over all groups); diag_sum_dev (fp64) = the sum of diag in row order.  The table is read on the device and clamped there (offsets
+ * into [0, N], ends to their begins, sizes to max_group_rows): a corrupt table gives wrong ranks, never an access out of bounds; rows
+ * that no group covers are not written.  A row's rank and diag do not depend on the other groups.  Two launches. */
+int mdm_retrieval_ranks(const float* q_dev, const float* c_dev, int32_t N, int32_t D, const int32_t* group_offsets_dev,
+                        int32_t n_groups, int32_t max_group_rows, int32_t top_k, int32_t* rank_dev, float* diag_dev,
+                        int64_t* topk_count_dev, double* diag_sum_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* out_dev[i][j] = sqrt(d2(a_dev[i], b_dev[j])) for a_dev [NA, D], b_dev [NB, D], out_dev [NA, NB] fp32 (euclidean_distance_matrix
+ * without the Gram form's cancellation: exactly 0 for equal rows, never NaN for finite rows).  NA * NB < 2^31.  One launch. */
+int mdm_dist_matrix(const float* a_dev, int32_t NA, const float* b_dev, int32_t NB, int32_t D, float* out_dev, void* workspace_dev,
+                    size_t workspace_bytes, void* stream);
+
+/* pred_dev[n] = argmax_c yhat_dev[n][c] for yhat_dev [N, C]: the lowest index among equal maxima, a NaN counts as the maximum and the
+ * first NaN wins (what the reference's `.max(dim=1).indices` returns on the host).  confusion_dev [C, C] (int64): [labels_dev[n]][pred_dev[n]] += 1 -- the call ADDS to
+ * the matrix, which the caller zeroes once and may then feed batch by batch (integer atomics: the result does not depend on their
+ * order).  A label outside [0, C) is not counted; it adds 1 to bad_dev (int32, also accumulated).  N * C, C * C < 2^31.  One launch. */
+int mdm_confusion(const float* yhat_dev, const int32_t* labels_dev, int32_t N, int32_t C, int32_t* pred_dev, int64_t* confusion_dev,
+                  int32_t* bad_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- SMPLify: fitting SMPL to 22 generated joints per frame (visualize/simplify_loc2rot.py joints2smpl over
  * visualize/joints2smpl/src/smplify.py SMPLify3D, use_lbfgs=True, use_collision=False, joints_category="AMASS", seq_ind = 0).

@@ -764,6 +764,23 @@ template <int N> __device__ __forceinline__ void wait_vmem_upto() {   // vmcnt(N
 #endif
 }
 
+// Integer counters in global memory that several workgroups add to (humanml_metrics.h confusion_kernel): the sum does not depend on
+// the order of the additions.  The emulator runs its fibers one at a time.
+__device__ __forceinline__ void atomic_add_i64(long long* p, long long v) {
+#ifdef MDM_EMU
+  *p += v;
+#else
+  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
+#endif
+}
+__device__ __forceinline__ void atomic_add_i32(int* p, int v) {
+#ifdef MDM_EMU
+  *p += v;
+#else
+  atomicAdd(p, v);
+#endif
+}
+
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
 // x sigmoid(a x): SiLU at a = 1 (1.0f * x is x: silu's bits) and clip/model.py's QuickGELU at a = 1.702, on one copy of the code

@@ -1,5 +1,6 @@
 // metrics_api.h -- part of the ONE translation unit csrc/mdm_api.hip: mdm_metrics_workspace_bytes, mdm_knn_radius,
 // mdm_manifold_members, mdm_gather_dist, mdm_poly_mmd and mdm_feature_stats (include/mdm_hip.h) over the kernels of metrics.h.
+// (humanml_metrics_api.h, included behind this file, shares the checks below and the workspace sizes.)
 #pragma once
 // (included by mdm_api.hip behind its other entry points; relies on its includes, api_runtime.h and `using namespace mdm`)
 
@@ -45,7 +46,7 @@ extern "C" {
 
 size_t mdm_metrics_workspace_bytes(int32_t kind, int32_t rows, int32_t subsets) {
   const char* f = "mdm_metrics_workspace_bytes: ";
-  if (kind < MDM_METRICS_KNN_RADIUS || kind > MDM_METRICS_FEATURE_STATS) { fail(MDM_EINVAL, std::string(f) + "unknown kind"); return 0; }
+  if (kind < MDM_METRICS_KNN_RADIUS || kind > MDM_METRICS_CONFUSION) { fail(MDM_EINVAL, std::string(f) + "unknown kind"); return 0; }
   if (rows < 1) { fail(MDM_EINVAL, std::string(f) + "rows must be at least 1"); return 0; }
   if (kind != MDM_METRICS_POLY_MMD) return ws_bytes_of(0);
   if (subsets < 1) { fail(MDM_EINVAL, std::string(f) + "subsets must be at least 1"); return 0; }
