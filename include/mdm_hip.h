@@ -784,6 +784,32 @@ int mdm_dist_matrix(const float* a_dev, int32_t NA, const float* b_dev, int32_t 
 int mdm_confusion(const float* yhat_dev, const int32_t* labels_dev, int32_t N, int32_t C, int32_t* pred_dev, int64_t* confusion_dev,
                   int32_t* bad_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- The Frechet distance of two Gaussians on the device (calculate_frechet_distance of eval/a2m/action2motion/fid.py and
+ * data_loaders/humanml/utils/metrics.py), in fp64, from the statistics mdm_feature_stats writes.  (Additive to ABI 10.)
+ *
+ * Tr sqrtm(sigma1 sigma2) = sum_i sqrt(lambda_i(M)), M = S^T sigma2 S, S = V diag(sqrt(max(w, 0))), sigma1 = V diag(w) V^T: two
+ * symmetric eigen-solves (two-sided cyclic Jacobi on a round-robin schedule; the first with vectors) and two D x D x D products on
+ * v_mfma_f64_16x16x4_f64 between them.  Both covariances are taken by their symmetric parts (s_ij + s_ji) / 2.  No complex
+ * arithmetic, no division by a small eigenvalue, no eps retry: a singular product is finite.  D <= 64 (rounded up to even): each
+ * solve is one launch of one workgroup; above: one launch per round of D - 1 (D odd: D) rounds per sweep, 30 sweeps enqueued, every
+ * launch behind the first sweep that rotated nothing returns at once (convergence is detected on the device; nothing is read back).
+ *
+ * result4_dev (fp64): [0] = |mu1 - mu2|^2 + Tr sigma1 + Tr sigma2 - 2 [1];  [1] = sum_i sqrt(max(lambda_i, 0));  [2] = min w / max w
+ * of sigma1;  [3] = min lambda / max lambda of M (a spectrum without a positive value: 0 when it is all zero, -inf when it holds a
+ * negative one).  sweeps2_dev (int32): per solve, the sweeps that performed a rotation; 30: the solve did not converge, and then
+ * result4_dev is NaN, never a plausible number.  Every sum is fp64 in a fixed order; the only atomics count rotations: repeated
+ * calls return the same bits.  Refused with a message before anything is launched: a null pointer, an fp64 pointer off an 8-byte
+ * boundary, D outside 1 .. 1024, a missing workspace, one below mdm_frechet_workspace_bytes (MDM_ENOSPC).  Joins the
+ * one-chain-per-device guard (CONCURRENCY).  No device allocation, no synchronisation, every kernel on `stream`: capture-safe after
+ * one warm-up call of a D <= 64 outside the capture (the one-workgroup solve opts in to 66 KB of LDS at its first use). */
+
+/* Bytes of workspace of mdm_frechet_distance at D features: 64 + 1 KB + 16 KB + seven fp64 matrices of D (rounded up to even)
+ * squared; 0 for D < 1 or D > 1024 (mdm_last_error says so). */
+size_t mdm_frechet_workspace_bytes(int32_t D);
+
+int mdm_frechet_distance(const double* mu1_dev, const double* sigma1_dev, const double* mu2_dev, const double* sigma2_dev, int32_t D,
+                         double* result4_dev, int32_t* sweeps2_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- SMPLify: fitting SMPL to 22 generated joints per frame (visualize/simplify_loc2rot.py joints2smpl over
  * visualize/joints2smpl/src/smplify.py SMPLify3D, use_lbfgs=True, use_collision=False, joints_category="AMASS", seq_ind = 0).
  * (Additive to ABI 10.)

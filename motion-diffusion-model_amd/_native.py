@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "mdm_clip_text_workspace_bytes", "mdm_clip_text_encode",
     "mdm_metrics_workspace_bytes", "mdm_knn_radius", "mdm_manifold_members", "mdm_gather_dist", "mdm_poly_mmd", "mdm_feature_stats",
     "mdm_retrieval_ranks", "mdm_dist_matrix", "mdm_confusion",
+    "mdm_frechet_workspace_bytes", "mdm_frechet_distance",
     "mdm_smplify_workspace_bytes", "mdm_smplify_value_grad", "mdm_smplify_fit", "mdm_smplify_strong_wolfe",
 ]
 # include/mdm_hip_probe.h: exported by the probe build only
@@ -152,6 +153,7 @@ METRICS_KINDS = {"knn_radius": 0, "manifold_members": 1, "gather_dist": 2, "poly
                  "retrieval_ranks": 5, "dist_matrix": 6, "confusion": 7}      # MDM_METRICS_*
 RETRIEVAL_TOPK_MAX = 16     # csrc/humanml_metrics.h RET_TOPK_MAX
 METRICS_TILE = 64           # csrc/metrics.h MET_TILE
+FRECHET_MAX_D, FRECHET_SMALL_MAX, FRECHET_MAX_SWEEPS = 1024, 64, 30      # csrc/frechet.h FR_MAX_D, FR_SMALL_MAX, FR_MAX_SWEEPS
 STGCN_RES = {"none": 0, "identity": 1, "conv": 2}      # MDM_STGCN_RES_*
 STGCN_MAX_BLOCKS, STGCN_MAX_NEIGHBOURS = 16, 8
 
@@ -255,6 +257,8 @@ class MdmLib:
             "mdm_retrieval_ranks": (C.c_int, [vp, vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
             "mdm_dist_matrix": (C.c_int, [vp, i32, vp, i32, i32, vp, vp, sz, vp]),
             "mdm_confusion": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
+            "mdm_frechet_workspace_bytes": (sz, [i32]),
+            "mdm_frechet_distance": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
             "mdm_smplify_workspace_bytes": (sz, [P(MdmSmplifyModel), P(MdmSmplifyCall), i32]),
             "mdm_smplify_value_grad": (C.c_int, [P(MdmSmplifyModel), P(MdmSmplifyCall), i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp,
                                                  P(f32), vp, sz, vp]),

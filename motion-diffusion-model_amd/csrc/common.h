@@ -289,6 +289,30 @@ __device__ __forceinline__ f32x4 mfma16_f32(float a, float b, f32x4 c) {
 #endif
 }
 
+// v_mfma_f64_16x16x4_f64 (frechet.h): lane l supplies A[i = l&15][k = l>>4] and B[k = l>>4][j = l&15], one fp64 value each, as the
+// fp32 form above -- but the result map is the f64 instruction's own: D[reg] is row (l>>4) + 4 reg, column l&15.
+// The emulator: a plain loop over that lane map, k ascending, one fused multiply-add per k (the lanes' operands cross through a
+// per-wave buffer: the workgroups of a launch run one at a time there).
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f64x4 mfma16_f64(double a, double b, f64x4 c) {
+#ifdef MDM_EMU
+  static double xa[16][64], xb[16][64];
+  const int l = emu::lane_id(), w = emu::wave_id() & 15, j = l & 15, q = l >> 4;
+  xa[w][l] = a;
+  xb[w][l] = b;
+  emu::wave_barrier();
+  for (int r = 0; r < 4; ++r) {
+    double acc = c[r];
+    for (int k = 0; k < 4; ++k) acc = fma(xa[w][q + 4 * r + 16 * k], xb[w][j + 16 * k], acc);
+    c[r] = acc;
+  }
+  emu::wave_barrier();
+  return c;
+#else
+  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+#endif
+}
+
 // Two v_mfma_f32_32x32x16_f16 operand fragments of the same 32 rows -- w0: k 0-15, w1: k 16-31 -- become the two
 // v_mfma_f32_16x16x32_f16 fragments over the same 32 k -- w0: rows 0-15, w1: rows 16-31.  As rows of 16 lanes,
 //   in   w0 = [r0-15 k0-7 | r16-31 k0-7 | r0-15 k8-15 | r16-31 k8-15]    w1 = the same with k + 16

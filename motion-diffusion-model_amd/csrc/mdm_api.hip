@@ -41,6 +41,7 @@
 #include "gru_recogniser.h"
 #include "metrics.h"
 #include "humanml_metrics.h"
+#include "frechet.h"
 #include "smplify.h"
 
 using namespace mdm;
@@ -284,7 +285,7 @@ int mdm_attention_x3(const float* qkv, float* out, const int32_t* lengths, int32
 
 // The entry points that are not MDM's own, one file per model (each with its helpers in an anonymous namespace): the probe
 // library's, then SMPL, the HumanML3D evaluator, the two text encoders, ST-GCN, the GRU recogniser, the
-// metrics of the unconstrained, the HumanML3D and the a2m evaluations, and the SMPLify fit.
+// metrics of the unconstrained, the HumanML3D and the a2m evaluations, the Frechet distance, and the SMPLify fit.
 #ifdef MDM_PROBES
 #include "probe_api.h"
 #endif
@@ -295,4 +296,5 @@ int mdm_attention_x3(const float* qkv, float* out, const int32_t* lengths, int32
 #include "gru_recogniser_api.h"
 #include "metrics_api.h"
 #include "humanml_metrics_api.h"
+#include "frechet_api.h"
 #include "smplify_api.h"

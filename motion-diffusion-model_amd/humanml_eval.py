@@ -7,6 +7,9 @@ What differs is where the data lives.  Per loader the text and motion embeddings
 `retrieval` call covers every batch (the batch sizes travel as host integers); `activation_dict` holds device tensors, which
 `evaluate_fid` and `evaluate_diversity` take as they are.  Nothing is copied to the host per batch; what reaches the host per loader
 is four numbers (the matching-score sum and three counts), the D x D statistics for scipy's sqrtm, and one mean per metric.
+With the module switch `FID_ON_DEVICE = True` (off by default; a switch and not a keyword, because `evaluate_fid` and `evaluation`
+keep the reference's parameter lists) the distance is `hm.frechet_distance_device`'s: the statistics stay on the device and one
+scalar comes back.
 
 `eval_wrapper` is any object with the reference's `get_co_embeddings(word_embs=, pos_ohot=, cap_lens=, motions=, m_lens=)` and
 `get_motion_embeddings(motions=, m_lens=)` that returns device tensors (mdm_amd.evaluator.EvaluatorMDMWrapper)."""
@@ -19,6 +22,7 @@ import torch
 from . import humanml_metrics as hm
 
 TOP_K = 3
+FID_ON_DEVICE = False      # True: evaluate_fid takes hm.frechet_distance_device(...).item() instead of the host formula (scipy sqrtm)
 
 
 def _say(line, file):
@@ -65,7 +69,10 @@ def evaluate_fid(eval_wrapper, groundtruth_loader, activation_dict, file):
     gt_mu, gt_cov = hm.calculate_activation_statistics(torch.cat(gt_motion_embeddings, dim=0))
     for model_name, motion_embeddings in activation_dict.items():
         mu, cov = hm.calculate_activation_statistics(motion_embeddings)
-        fid = hm.calculate_frechet_distance(gt_mu, gt_cov, mu, cov)
+        if FID_ON_DEVICE:
+            fid = hm.frechet_distance_device(gt_mu, gt_cov, mu, cov).item()
+        else:
+            fid = hm.calculate_frechet_distance(gt_mu, gt_cov, mu, cov)
         _say(f'---> [{model_name}] FID: {fid:.4f}', file)
         eval_dict[model_name] = fid
     return eval_dict

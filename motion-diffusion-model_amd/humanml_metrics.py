@@ -5,7 +5,7 @@ data_loaders/humanml/utils/metrics.py: `euclidean_distance_matrix`, `calculate_t
 Features are device tensors and stay there: the arithmetic is csrc/humanml_metrics.h (mdm_retrieval_ranks, mdm_dist_matrix) and
 csrc/metrics.h (mdm_gather_dist, mdm_feature_stats), with no torch / numpy distance and no fall-back when the library is missing.
 On the host: the random draws (numpy's global generator, the reference's calls in the reference's order) and the matrix square root
-of `calculate_frechet_distance`.
+of `calculate_frechet_distance`, the default; `frechet_distance_device` is the same distance on the device (csrc/frechet.h).
 
 Differences from upstream: distances are direct differences in fp32 (upstream: the Gram form, which cancels and returns nan for
 equal rows); ranks are positions in a STABLE ascending sort (upstream's np.argsort is quicksort: the same wherever a row has no tie);
@@ -18,6 +18,7 @@ from . import _native as nat
 from . import metrics as _m
 from ._native_model import native_stream
 from .metrics import calculate_activation_statistics, calculate_frechet_distance, gather_dist      # noqa: F401  (upstream's names)
+from .metrics import calculate_fid_device, frechet_distance_device      # noqa: F401  (the device option of the distance)
 
 MATCHING_GROUP_ROWS = 64      # calculate_matching_score's groups: one row tile each (a row's distance does not depend on its group)
 

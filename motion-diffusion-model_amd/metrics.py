@@ -5,7 +5,11 @@
 (eval/a2m/action2motion/diversity.py).  The features stay on the device: the arithmetic is csrc/metrics.h behind include/mdm_hip.h's
 mdm_knn_radius, mdm_manifold_members, mdm_gather_dist, mdm_poly_mmd and mdm_feature_stats (no torch.norm / sklearn call, and no
 fall-back when the library is missing).  What stays on the host: the random draws (numpy's global generator, in upstream's order, so
-a seeded run uses upstream's subsets and pairs) and `calculate_fid`'s matrix square root of a D x D matrix (scipy).
+a seeded run uses upstream's subsets and pairs) and, by default, `calculate_fid`'s matrix square root of a D x D matrix (scipy:
+`calculate_frechet_distance` is upstream's host formula, bit for bit).  The option: `frechet_distance_device` / `calculate_fid_device`
+evaluate the same distance on the device in fp64 (csrc/frechet.h behind mdm_frechet_distance: two Jacobi eigen-solves and two MFMA
+products instead of sqrtm) and return a device scalar; the evaluation loops take them on request (`unconstrained_eval`: `fid_on_device=True`; `humanml_eval`:
+the module switch `FID_ON_DEVICE`).
 
 Differences from upstream: precision / recall compare squared distances (fp32, direct differences) with squared radii instead of
 `torch.norm` values with fp64 copies of them; KID forms the Gram products in fp32 and everything behind them in fp64 (upstream: fp32
@@ -212,6 +216,66 @@ def calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
 
 def calculate_fid(statistics_1, statistics_2):
     return calculate_frechet_distance(statistics_1[0], statistics_1[1], statistics_2[0], statistics_2[1])
+
+
+IMAG_TOL = 1e-3            # upstream's np.allclose(np.diagonal(covmean).imag, 0, atol=1e-3)
+
+
+def frechet_distance_device(mu1, sigma1, mu2, sigma2, check=True):
+    """The Frechet distance as a 0-dim fp64 tensor on the inputs' device, from fp64 device statistics (what
+    `calculate_activation_statistics` returns): Tr sqrtm(sigma1 sigma2) = sum sqrt(eig(S^T sigma2 S)), S S^T = sigma1, by two symmetric
+    eigen-solves in one native call.  Both covariances count by their symmetric parts; negative eigenvalues are clamped to 0.
+    check=True reads the call's result block (one synchronisation) and raises ValueError when a solve did not converge, when the result is not finite or when the
+    product has a negative eigenvalue with sqrt(-lambda_min) > 1e-3 -- upstream's "Imaginary component" refusal, tested on the bound
+    sqrt(-lambda_min / lambda_max) sum sqrt(lambda) >= sqrt(-lambda_min) the block allows.  check=False touches nothing on the host: a
+    solve that did not converge returns NaN."""
+    lib = _lib()
+    names = ("mu1", "sigma1", "mu2", "sigma2")
+    for name, t in zip(names, (mu1, sigma1, mu2, sigma2)):
+        if not torch.is_tensor(t):
+            if lib.path.endswith(nat.LIB_NAME):
+                raise nat.MdmError(f"the MI355X HIP path needs {name} on a cuda (ROCm) device; got a {type(t).__name__} on the host")
+            raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+    mu1, mu2 = (t.detach().reshape(-1) if t.dim() == 0 else t.detach() for t in (mu1, mu2))
+    sigma1, sigma2 = (t.detach().reshape(1, 1) if t.dim() == 0 else t.detach() for t in (sigma1, sigma2))
+    if mu1.shape != mu2.shape:
+        raise ValueError(f"the mean vectors have different lengths: {tuple(mu1.shape)} and {tuple(mu2.shape)}")
+    if sigma1.shape != sigma2.shape:
+        raise ValueError(f"the covariances have different dimensions: {tuple(sigma1.shape)} and {tuple(sigma2.shape)}")
+    D = mu1.shape[0] if mu1.dim() == 1 else -1
+    if D < 1 or tuple(sigma1.shape) != (D, D):
+        raise ValueError(f"mu1 must be [D] and sigma1 [D, D], got {tuple(mu1.shape)} and {tuple(sigma1.shape)}")
+    stream = native_stream(lib, mu1, "mu1")
+    args = []
+    for name, t in zip(names, (mu1, sigma1, mu2, sigma2)):
+        if t.device != mu1.device:
+            raise ValueError(f"{name} is on {t.device}, mu1 on {mu1.device}")
+        if t.dtype != torch.float64:
+            raise ValueError(f"{name} must be float64 (calculate_activation_statistics returns it), got {t.dtype}")
+        args.append(t.contiguous())
+    nbytes = lib.mdm_frechet_workspace_bytes(D)
+    if nbytes == 0:
+        lib.check(-1, "mdm_frechet_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=mu1.device)
+    result = torch.empty(4, dtype=torch.float64, device=mu1.device)
+    sweeps = torch.empty(2, dtype=torch.int32, device=mu1.device)
+    lib.check(lib.mdm_frechet_distance(args[0].data_ptr(), args[1].data_ptr(), args[2].data_ptr(), args[3].data_ptr(), D, result.data_ptr(),
+                                       sweeps.data_ptr(), ws.data_ptr(), nbytes, stream), "mdm_frechet_distance")
+    if check:
+        r, sw = result.cpu().numpy(), sweeps.cpu().numpy()
+        if sw.max() >= nat.FRECHET_MAX_SWEEPS:
+            raise ValueError(f"the eigen-solves of sigma1 / of the product ran {sw.tolist()} sweeps: no convergence within "
+                             f"{nat.FRECHET_MAX_SWEEPS} (non-finite statistics?)")
+        if not np.isfinite(r[0]):
+            raise ValueError(f"the Frechet distance is not finite ({r[0]}): the statistics hold a value that is not finite")
+        imag = np.inf if r[3] == -np.inf else (np.sqrt(-r[3]) * r[1] if r[3] < 0 else 0.0)
+        if not imag <= IMAG_TOL:
+            raise ValueError(f"Imaginary component {imag}: sigma1 sigma2 has a negative eigenvalue (min / max = {r[3]:.3e})")
+    return result[0]
+
+
+def calculate_fid_device(statistics_1, statistics_2, check=True):
+    return frechet_distance_device(statistics_1[0], statistics_1[1], statistics_2[0], statistics_2[1], check=check)
 
 
 # ---- diversity --------------------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 every metric behind it (`mdm_amd.metrics`) run on the device, so the features never leave it and precision / recall is no longer the
 part a `fast` run has to skip.  Same root-joint centring, batches of 64, order of the random draws (KID, then the diversity of the
 dataset, then of the generated motions) and result dictionary as upstream.  Differences: the caller's `generated_motions` is not
-modified (upstream centres it in place); the batches are slices, not a DataLoader with worker processes; the progress prints are gone."""
+modified (upstream centres it in place); the batches are slices, not a DataLoader with worker processes; the progress prints are gone;
+`fid_on_device=True` (off by default) takes the FID from `metrics.calculate_fid_device` instead of scipy's sqrtm on the host."""
 import numpy as np
 import torch
 
@@ -46,7 +47,7 @@ def compute_features(model, motions, device):
 
 
 def evaluate_unconstrained_metrics(generated_motions, device, fast, act_rec_model_path=ACT_REC_MODEL_PATH, dataset_path=DATASET_PATH,
-                                   kid_subsets=metrics.KID_SUBSETS, kid_subset_size=metrics.KID_SUBSET_SIZE):
+                                   kid_subsets=metrics.KID_SUBSETS, kid_subset_size=metrics.KID_SUBSET_SIZE, fid_on_device=False):
     act_rec_model = initialize_model(device, act_rec_model_path)
 
     generated_features, _ = compute_features(act_rec_model, centre_root(generated_motions), device)
@@ -56,7 +57,10 @@ def evaluate_unconstrained_metrics(generated_motions, device, fast, act_rec_mode
     dataset_features, _ = compute_features(act_rec_model, centre_root(motion_data), device)
     real_stats = metrics.calculate_activation_statistics(dataset_features)
 
-    fid = metrics.calculate_fid(generated_stats, real_stats)
+    if fid_on_device:
+        fid = metrics.calculate_fid_device(generated_stats, real_stats).item()
+    else:
+        fid = metrics.calculate_fid(generated_stats, real_stats)
     kid = metrics.calculate_kid(dataset_features, generated_features, n_subsets=kid_subsets, subset_size=kid_subset_size)
     dataset_diversity = metrics.calculate_diversity(dataset_features)
     generated_diversity = metrics.calculate_diversity(generated_features)

@@ -12,6 +12,14 @@ profiles/r18a_metrics.md:
 There is no speed gate: the note is the record.
 
     python tools/bench_metrics.py [--calls 10] [--pr-rows 250] [--reference PATH] [--out profiles/r18a_metrics.md]
+
+With --frechet it measures the two FID paths instead and writes profiles/r19a_frechet.md: `calculate_fid` (the host path: the device
+statistics copied to the host, scipy's sqrtm) against `calculate_fid_device(check=False)` followed by one synchronise, interleaved
+call by call, at D = 30, 256 and 512; per D the sweeps both solves used, the launches the call enqueues, the host time of the
+enqueue alone, and the same call on diagonal statistics, where every launch behind the first sweep returns at once (the price of the
+sweeps that are enqueued and not needed).
+
+    python tools/bench_metrics.py --frechet [--calls 10] [--out profiles/r19a_frechet.md]
 """
 import argparse
 import os
@@ -111,14 +119,84 @@ def once(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
+FRECHET_SIZES = ((30, 1000), (256, 1000), (512, 4000))      # (D, N): the GRU recogniser's, the ST-GCN's and the HumanML3D evaluator's widths
+
+
+def frechet_launches(D):
+    """Kernel launches mdm_frechet_distance enqueues at D (csrc/frechet_api.h)."""
+    n = (D + 1) & ~1
+    solve = 2 if n <= 64 else 1 + 30 * (n - 1) + 1
+    return 2 + solve + 1 + 2 + 1 + solve + 1
+
+
+def spread(v):
+    return f"{statistics.median(v):.3f} | {min(v):.3f} | {max(v):.3f}"
+
+
+def frechet_main(a):
+    import frechet_helpers as fh
+    from mdm_amd import _native as nat
+    from mdm_amd import metrics as M
+    lib = nat.load_native()
+    out = a.out if a.out else os.path.join(ROOT, "profiles", "r19a_frechet.md")
+    lines = ["# r19a — the Frechet distance on the device (csrc/frechet.h) against the host path, on the MI355X", "",
+             f"Device: {torch.cuda.get_device_name(0)}, torch {torch.__version__}.  Written by `tools/bench_metrics.py --frechet`.", "",
+             f"Per D: seeded anisotropic Gaussians (tests/frechet_helpers.py make_sets), statistics from `calculate_activation_statistics` "
+             f"on the device; two warm calls of each path, then {a.calls} calls of each, interleaved host / device call by call.  `host`: "
+             "`calculate_fid` on the device statistics (copy to the host included, scipy sqrtm).  `device`: "
+             "`calculate_fid_device(check=False)` and one synchronise; `enqueue` is the host time of that call before the synchronise; "
+             "`diagonal`: the same call on diagonal covariances, where no sweep rotates and all launches behind sweep 0 return at once.", "",
+             "| D | N | host ms median | min | max | device ms median | min | max | enqueue ms median | min | max | diagonal ms median | min | max "
+             "| sweeps | launches | host / device | abs(device - host) / S |", "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for D, N in FRECHET_SIZES:
+        x1, x2 = fh.make_sets(D, N, 8200 + D)
+        s1 = M.calculate_activation_statistics(torch.from_numpy(x1).to(DEV))
+        s2 = M.calculate_activation_statistics(torch.from_numpy(x2).to(DEV))
+        dg1, dg2 = (s1[0], torch.diag(torch.diagonal(s1[1])).contiguous()), (s2[0], torch.diag(torch.diagonal(s2[1])).contiguous())
+        host_np = [t.cpu().numpy() for t in (*s1, *s2)]
+        _, sw = fh.raw_call(lib, DEV, *host_np)
+        for _ in range(2):
+            ref = M.calculate_fid(s1, s2)
+            got = M.calculate_fid_device(s1, s2, check=False)
+            M.calculate_fid_device(dg1, dg2, check=False)
+        torch.cuda.synchronize()
+        host, dev, enq, diag = [], [], [], []
+        for _ in range(a.calls):
+            t0 = time.perf_counter()
+            ref = M.calculate_fid(s1, s2)
+            host.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            got = M.calculate_fid_device(s1, s2, check=False)
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            dev.append((time.perf_counter() - t0) * 1e3)
+            enq.append((t1 - t0) * 1e3)
+            t0 = time.perf_counter()
+            M.calculate_fid_device(dg1, dg2, check=False)
+            torch.cuda.synchronize()
+            diag.append((time.perf_counter() - t0) * 1e3)
+        S = fh.scale_of(*host_np)
+        lines.append(f"| {D} | {N} | {spread(host)} | {spread(dev)} | {spread(enq)} | {spread(diag)} | {sw.tolist()} | {frechet_launches(D)} | "
+                     f"{statistics.median(host) / statistics.median(dev):.2f} x | {abs(got.item() - ref) / S:.2e} |")
+    lines += ["", "Not measured: per-kernel times (no traced run) and the share of any peak.  No speed gate applies; the option is off by "
+              "default.", ""]
+    with open(out, "w") as fh_out:
+        fh_out.write("\n".join(lines))
+    print("\n".join(lines))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--pr-rows", type=int, default=250)
     ap.add_argument("--reference", default=None, help="a checkout of the reference: time its own functions instead of the restatements")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r18a_metrics.md"))
+    ap.add_argument("--out", default=None, help="default: profiles/r18a_metrics.md (with --frechet: profiles/r19a_frechet.md)")
+    ap.add_argument("--frechet", action="store_true", help="measure the two FID paths instead (profiles/r19a_frechet.md)")
     a = ap.parse_args()
     assert torch.cuda.is_available()
+    if a.frechet:
+        return frechet_main(a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "r18a_metrics.md")
     from mdm_amd import metrics as M
 
     if a.reference:
