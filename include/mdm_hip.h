@@ -377,6 +377,67 @@ int mdm_attention_x3(const float* qkv_dev, float* out_dev, const int32_t* length
 int mdm_recover_from_ric(const float* x_dev, const float* mean_dev, const float* std_dev, float* out_dev, int32_t B,
                          int32_t T, int32_t njoints_feat, int32_t joints, void* stream);
 
+/* The inverse of mdm_recover_from_ric, on the device: joint positions -> HumanML3D / KIT feature vectors (additive to ABI 10;
+ * kernels: csrc/motion_features.h).  Restates
+ *   extract_features(positions, feet_thre, ...)   (data_loaders/humanml/scripts/motion_process.py:43-170)
+ *   process_file(positions, feet_thre)            (motion_process.py:173-355; uniform_skeleton :17-40)
+ *   Skeleton.inverse_kinematics_np / forward_kinematics_np   (data_loaders/humanml/common/skeleton.py:55-104, :129-150)
+ * and the quaternion helpers they use (data_loaders/humanml/common/quaternion.py: qbetween, qnormalize, qmul, qinv, qrot,
+ * quaternion_to_cont6d).  The foot contacts are computed in fp32 exactly as numpy computes them on fp32 positions (bit-exact flags);
+ * everything else in fp64, rounded once at the store.  Where the reference's qbetween crosses along the frame axis for a clip of
+ * exactly 3 frames (its cross product is called without an axis), this call crosses over xyz.
+ *
+ * The skeleton tables are HOST data (utils/paramUtil.py:4-55; motion_process.py:460-466, :506-512): the kinematic chains -- chain 0
+ * starts at the root, joint 0; every other chain at a joint an earlier chain reaches; every other joint is reached once --, the raw
+ * offsets (unit axes), the face joints in the reference's list order, the foot joints, the two leg bones of the retargeting ratio. */
+#define MDM_SKEL_MAX_JOINTS 22
+#define MDM_SKEL_MAX_CHAINS 8
+#define MDM_SKEL_MAX_CHAIN_LEN 8
+typedef struct mdm_skeleton {
+  int32_t joints;                                            /* J <= 22                                   */
+  int32_t n_chains;
+  int32_t chain_len[MDM_SKEL_MAX_CHAINS];
+  int32_t chains[MDM_SKEL_MAX_CHAINS][MDM_SKEL_MAX_CHAIN_LEN];
+  float raw_offsets[MDM_SKEL_MAX_JOINTS][3];
+  int32_t face_joints[4];                                    /* face_joint_indx: r_hip, l_hip, sdr_r, sdr_l */
+  int32_t fid_r[2], fid_l[2];
+  int32_t l_idx1, l_idx2;
+} mdm_skeleton_t;
+
+#define MDM_J2F_LAYOUT_BJ3T 0   /* joints_dev [B, J, 3, T]: what mdm_recover_from_ric emits */
+#define MDM_J2F_LAYOUT_BTJ3 1   /* joints_dev [B, T, J, 3]: the reference's per-clip layout  */
+
+/* process_file's steps, each selectable (all off: extract_features on the positions as they are):
+ *   tgt_offsets   HOST [J][3] or null: uniform_skeleton -- IK with the unsmoothed forward, the root scaled by the leg-length ratio of
+ *                 frame 0, FK along these offsets (what Skeleton.get_offsets_joints returns for the target clip);
+ *   floor         subtract the minimum y over all valid frames and joints of the clip;
+ *   origin_xz     move the root's xz of frame 0 to the origin;
+ *   face_z        rotate the clip so that frame 0 faces +Z.
+ * mean_dev / std_dev [F] or both null: the output is (x - mean) / std.  global_dev / ric_dev, optional [B, J, 3, T]: the positions
+ * the features were taken from (process_file's global_positions) and the rotation-invariant positions of every valid frame (its
+ * third result); zeros beyond a clip's length. */
+typedef struct mdm_joints_to_features_call {
+  int32_t layout;
+  int32_t floor, origin_xz, face_z;
+  double feet_thre;                                          /* 0.002 HumanML3D, 0.05 KIT                  */
+  const float* tgt_offsets;
+  const float* mean_dev;
+  const float* std_dev;
+  float* global_dev;
+  float* ric_dev;
+} mdm_joints_to_features_call_t;
+
+/* joints_dev as `layout` says, fp32; lengths HOST [B] or null (every clip has T frames), 2 <= lengths[b] <= T; out_dev
+ * [B, F, 1, T - 1] with F = 12 J - 1 (263 for 22 joints, 251 for 21): frames >= lengths[b] - 1 of a clip are exact zeros, and nothing
+ * read beyond lengths[b] influences a valid frame.  ws_dev (mdm_joints_to_features_workspace_bytes) holds the canonicalised
+ * positions in fp64; it may be null when no step of process_file is selected.  T <= 1024 (MDM_EUNSUPPORTED beyond: a clip's forward
+ * vectors are staged in LDS for the 161-tap temporal filter).  The frame counts travel as kernel arguments, 64 clips a launch: no
+ * allocation, no copy, capture-safe. */
+size_t mdm_joints_to_features_workspace_bytes(int32_t B, int32_t T, int32_t joints);
+int mdm_joints_to_features(const mdm_skeleton_t* skeleton, const mdm_joints_to_features_call_t* call, const float* joints_dev,
+                           const int32_t* lengths, float* out_dev, int32_t B, int32_t T, int32_t F, void* ws_dev, size_t ws_bytes,
+                           void* stream);
+
 /* Post-sampling transform of the rot6d (action-to-motion) families, on the device: the SMPL joint positions of
  *   model.rot2xyz(x, mask, pose_rep='rot6d', glob=True, translation=True, jointstype='smpl', vertstrans=True, beta=0)
  * (model/rotation2xyz.py:17-90, utils/rotation_conversions.py rotation_6d_to_matrix, smplx lbs batch_rigid_transform).

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "mdm_retrieval_ranks", "mdm_dist_matrix", "mdm_confusion",
     "mdm_frechet_workspace_bytes", "mdm_frechet_distance",
     "mdm_smplify_workspace_bytes", "mdm_smplify_value_grad", "mdm_smplify_fit", "mdm_smplify_strong_wolfe",
+    "mdm_joints_to_features_workspace_bytes", "mdm_joints_to_features",
 ]
 # include/mdm_hip_probe.h: exported by the probe build only
 PROBE_SYMBOLS = ["mdm_debug_set", "mdm_debug_get", "mdm_linear_f16f6", "mdm_linear_f16f6_scratch_bytes", "mdm_probe_in_proj",
@@ -145,6 +146,25 @@ class MdmSmplifyCall(C.Structure):
         kw.update(over)
         super().__init__(num_iters=num_iters, history=history, stage1_calls=stage1_calls,
                          stage2_calls=num_iters if stage2_calls is None else stage2_calls, **kw)
+
+
+SKEL_MAX_JOINTS, SKEL_MAX_CHAINS, SKEL_MAX_CHAIN_LEN = 22, 8, 8      # MDM_SKEL_MAX_*
+J2F_LAYOUTS = {"bj3t": 0, "btj3": 1}      # MDM_J2F_LAYOUT_*
+J2F_MAX_FRAMES = 1024       # csrc/motion_features.h kMfMaxT
+
+
+class MdmSkeleton(C.Structure):
+    """include/mdm_hip.h mdm_skeleton_t: the skeleton tables of mdm_joints_to_features (host data)."""
+    _fields_ = [("joints", C.c_int32), ("n_chains", C.c_int32), ("chain_len", C.c_int32 * SKEL_MAX_CHAINS),
+                ("chains", (C.c_int32 * SKEL_MAX_CHAIN_LEN) * SKEL_MAX_CHAINS), ("raw_offsets", (C.c_float * 3) * SKEL_MAX_JOINTS),
+                ("face_joints", C.c_int32 * 4), ("fid_r", C.c_int32 * 2), ("fid_l", C.c_int32 * 2), ("l_idx1", C.c_int32),
+                ("l_idx2", C.c_int32)]
+
+
+class MdmJointsToFeaturesCall(C.Structure):
+    """include/mdm_hip.h mdm_joints_to_features_call_t."""
+    _fields_ = [(n, C.c_int32) for n in ("layout", "floor", "origin_xz", "face_z")] + [("feet_thre", C.c_double),
+               ("tgt_offsets", C.POINTER(C.c_float))] + [(n, C.c_void_p) for n in ("mean_dev", "std_dev", "global_dev", "ric_dev")]
 
 
 SMPLIFY_FRAMES = 32         # csrc/smplify.h SMF_FRAMES: frames per workgroup
@@ -266,6 +286,8 @@ class MdmLib:
                                           vp, sz, vp]),
             "mdm_smplify_strong_wolfe": (C.c_int, [P(C.c_double), P(C.c_double), i32, C.c_double, C.c_double, C.c_double, C.c_double,
                                                    C.c_double, i32, i32, P(C.c_double), P(i32), P(C.c_double), P(C.c_double)]),
+            "mdm_joints_to_features_workspace_bytes": (sz, [i32, i32, i32]),
+            "mdm_joints_to_features": (C.c_int, [P(MdmSkeleton), P(MdmJointsToFeaturesCall), vp, P(i32), vp, i32, i32, i32, vp, sz, vp]),
         }
         probe_sig = {
             "mdm_debug_set": (C.c_int, [C.c_int, C.c_int]),

@@ -32,6 +32,7 @@
 #include "../../lab/csrc_probe/gemm_f16f6.h"
 #endif
 #include "motion_recover.h"
+#include "motion_features.h"
 #include "smpl_joints.h"
 #include "smpl_mesh.h"
 #include "evaluator.h"
@@ -284,12 +285,13 @@ int mdm_attention_x3(const float* qkv, float* out, const int32_t* lengths, int32
 }  // extern "C"
 
 // The entry points that are not MDM's own, one file per model (each with its helpers in an anonymous namespace): the probe
-// library's, then SMPL, the HumanML3D evaluator, the two text encoders, ST-GCN, the GRU recogniser, the
+// library's, then SMPL, joints to features, the HumanML3D evaluator, the two text encoders, ST-GCN, the GRU recogniser, the
 // metrics of the unconstrained, the HumanML3D and the a2m evaluations, the Frechet distance, and the SMPLify fit.
 #ifdef MDM_PROBES
 #include "probe_api.h"
 #endif
 #include "smpl_api.h"
+#include "motion_features_api.h"
 #include "evaluator_api.h"
 #include "text_api.h"
 #include "stgcn_api.h"
